@@ -6,7 +6,15 @@ through the public DAG API: native LHS fused into the 32 inverse-CDF kernels (no
 triang / poisson x 4, BASELINE config 2 set), then the Iman-Conover reorder of all 32 columns
 (rank + scores + Gram + decorrelate/correlate + rank + gather); outputs stay in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows ROWS] [--d COLS] [--cpu-n ROWS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows ROWS] [--d COLS] [--dump-outputs DIR]
+    python bench.py --full [--cpu-n ROWS] [--no-cpu] [--no-e2e] [--ppf-rows ROWS] ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step, the per-kernel HIP-event times read inside the timed steps).  --full adds every
+measurement that takes runs of its own: the one-stream standalone pass and the dominant kernel's
+roofline, the HBM copy ceiling, the end-to-end (D2H) call, the same-seed reference stream, the
+operator API, the ppf sweep and the CPU baseline.  --dump-outputs DIR writes a fixed, seeded
+sample of the rows of the last timed step's 32 columns to DIR/samples.npy (float64).
 
 With N > 1 (torch.distributed.run, one process per GPU, RCCL) the same N-row problem is
 row-sharded across the ranks (BASELINE config 4; strong scaling): rank r generates and
@@ -133,6 +141,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--rows", type=int, default=100_000_000)
     ap.add_argument("--d", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (standalone pass and roofline, HBM copy ceiling, end to "
+                         "end, reference stream, operator API, ppf sweep, CPU baseline); the options below "
+                         "size or skip them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a fixed, seeded sample of the rows of the last timed step's columns to "
+                         "DIR/samples.npy (float64; samples_rank<r>.npy with more than one GPU)")
     ap.add_argument("--cpu-n", type=int, default=1_000_000)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (D2H included) side measurement")
@@ -216,6 +231,8 @@ def main():
         with open(os.path.join(args.check_out, f"rank{rank}.json"), "w") as f:
             json.dump({"rank": rank, "world": world, "rows": n, "seed": args.seed + args.warmup + args.steps - 1,
                        "sha1": digests}, f)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ds, rank, world)
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -226,6 +243,40 @@ def main():
     # per-kernel device time inside the timed region (HIP events on the launching stream; the
     # step-4 lanes and the deferred counts run concurrently, so these durations are stretched)
     kernels = read_kernels(lib, n, d, args.steps)
+
+    # whole-step roofline: SURVEY.md §8(d)'s 96 algorithmic bytes per draw over the step time
+    # (the N-row job is row-sharded over `world` GPUs: n * d draws in all, against world x the peak)
+    pipeline = {"bytes_per_draw": 96, "achieved": round(96 * n * d / (ms_per_step / 1e3) / 1e9, 1),
+                "unit": "GB/s", "peak": HBM_PEAK_GBS * world,
+                "frac": round(96 * n * d / (ms_per_step / 1e3) / 1e9 / (HBM_PEAK_GBS * world), 4)}
+    side = side_measurements(args, lib, root, ds, base, C, step, barrier, world, rank, ms_per_step, pipeline) \
+        if args.full else {}
+
+    if rank == 0:
+        line = {"metric": "Msamples/s (N\u00d7d draws) + achieved HBM GB/s, LHS+ImanConover d=32",  # BASELINE.json
+                "value": round(value, 2),
+                "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+                "scaling": "strong" if world > 1 else "weak",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic (native LHS quantiles, seeded)",
+                "config": {"workload": ("cfg4: " if world > 1 else "cfg3: ") +
+                                       "d=32 (cfg2 set x4), LHS + ppf + ImanConover, N rows",
+                           "rows": n, "d": d,
+                           "parallelism": (f"row-sharded x{world} ({backend}: all-reduce + all-to-all of scores "
+                                           "out, positions back)") if world > 1 else "single",
+                           "devices": torch.cuda.device_count() if world > 1 else 1},
+                "pipeline_roofline": pipeline, "kernels": kernels}
+        line.update(side)
+        print(json.dumps(line))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def side_measurements(args, lib, root, ds, base, C, step, barrier, world, rank, ms_per_step, pipeline):
+    """--full: every measurement that takes runs of its own, after the timed steps (and after
+    --dump-outputs / --check-out read them).  Returns the keys it adds to the result line and
+    completes `pipeline` with the standalone kernel time and the measured-copy fraction."""
+    n, d = args.rows, args.d
 
     # the standalone pass (outside the timed region): one more step with every kernel on one
     # stream in order (pbh_set_serial: one step-4 lane, counts first), so each launch's duration
@@ -250,14 +301,8 @@ def main():
                 "kernel": dom, "avg_launch_ms": dk["avg_ms"], "bytes_per_launch": dk["bytes_per_launch"],
                 "duration_source": "standalone pass: pbh_set_serial(1), one stream, HIP events",
                 "valu_busy": valu, "valu_source": valu_src}
-
-    # whole-step roofline: SURVEY.md §8(d)'s 96 algorithmic bytes per draw over the step time
-    # (the N-row job is row-sharded over `world` GPUs: n * d draws in all, against world x the peak)
-    pipeline = {"bytes_per_draw": 96, "achieved": round(96 * n * d / (ms_per_step / 1e3) / 1e9, 1),
-                "unit": "GB/s", "peak": HBM_PEAK_GBS * world,
-                "frac": round(96 * n * d / (ms_per_step / 1e3) / 1e9 / (HBM_PEAK_GBS * world), 4),
-                "kernel_time_ms_per_step": round(sum(k["total_ms_per_step"] for k in standalone.values()), 3),
-                "kernel_time_source": "standalone pass (concurrent durations in `kernels` overlap)"}
+    pipeline["kernel_time_ms_per_step"] = round(sum(k["total_ms_per_step"] for k in standalone.values()), 3)
+    pipeline["kernel_time_source"] = "standalone pass (concurrent durations in `kernels` overlap)"
     copy_peak = hbm_copy_peak(lib) if rank == 0 else None
     if copy_peak:
         pipeline["frac_of_measured_copy"] = round(pipeline["achieved"] / copy_peak["GBps"], 4)
@@ -280,26 +325,34 @@ def main():
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args.cpu_n, d)
+    return {"roofline": roofline, "hbm_copy_peak": copy_peak, "end_to_end": e2e, "reference_stream": same_seed,
+            "operator_ic": op, "cpu_baseline": cpu, "ppf_sweep": sweep, "kernels_standalone": standalone}
 
-    if rank == 0:
-        line = {"metric": "Msamples/s (N\u00d7d draws) + achieved HBM GB/s, LHS+ImanConover d=32",  # BASELINE.json
-                "value": round(value, 2),
-                "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-                "scaling": "strong" if world > 1 else "weak",
-                "vs_baseline": None, "dtype": "f64", "data": "synthetic (native LHS quantiles, seeded)",
-                "config": {"workload": ("cfg4: " if world > 1 else "cfg3: ") +
-                                       "d=32 (cfg2 set x4), LHS + ppf + ImanConover, N rows",
-                           "rows": n, "d": d,
-                           "parallelism": (f"row-sharded x{world} ({backend}: all-reduce + all-to-all of scores "
-                                           "out, positions back)") if world > 1 else "single",
-                           "devices": torch.cuda.device_count() if world > 1 else 1},
-                "roofline": roofline, "pipeline_roofline": pipeline, "hbm_copy_peak": copy_peak,
-                "end_to_end": e2e, "reference_stream": same_seed, "operator_ic": op, "cpu_baseline": cpu, "ppf_sweep": sweep, "kernels": kernels,
-                "kernels_standalone": standalone}
-        print(json.dumps(line))
-    if dist is not None:
-        dist.destroy_process_group()
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: float64 bytes written in all (over every rank)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, ds, rank, world):
+    """--dump-outputs: what a caller of the timed step receives, the device-resident samples of
+    every column after the last timed step, as one (rows, d) float64 array DIR/samples.npy
+    (samples_rank<r>.npy: that rank's rows, with more than one GPU).  Beyond DUMP_BYTES a fixed
+    sample of the rows is kept: sorted indices drawn without replacement from a generator seeded
+    with DUMP_SEED, the same in every run with the same arguments."""
+    import numpy as np
+    import torch
+
+    cols = [x.samples_device.reshape(-1) for x in ds]
+    rows = cols[0].shape[0]
+    keep = max(1, DUMP_BYTES // (8 * len(cols) * world))
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+        idx = torch.from_numpy(idx).to(cols[0].device)
+        cols = [c.index_select(0, idx) for c in cols]
+    out = np.stack([c.to(torch.float64).cpu().numpy() for c in cols], axis=1)
+    os.makedirs(dirname, exist_ok=True)
+    name = "samples.npy" if world == 1 else f"samples_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), np.ascontiguousarray(out))
 
 
 def read_kernels(lib, n, d, steps):

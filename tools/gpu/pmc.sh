@@ -9,7 +9,7 @@ mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 300 rocprofv3 --pmc $C --kernel-include-regex 'pbh' -d $R/gpurun_out/pmc_${TAG}_$C -o pmc \
-    --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu --rows $ROWS \
+    --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu --rows $ROWS \
     > $R/gpurun_out/pmc_${TAG}_$C.log 2>&1
   rc=$?
   echo "pmc $C exit $rc"

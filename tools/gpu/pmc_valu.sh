@@ -22,8 +22,8 @@ run() {  # name, counters, program...
   timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctr -d $OUT/$name -o pmc --output-format csv -- "$@" > $OUT/$name.log 2>&1
   local rc=$?; echo "$name exit $rc"; return $rc
 }
-run bench_p1 "$P1" python3 $R/bench.py --steps 1 --warmup 0 --no-cpu --no-e2e --rows $ROWS || exit $?
-run bench_p2 "$P2" python3 $R/bench.py --steps 1 --warmup 0 --no-cpu --no-e2e --rows $ROWS || exit $?
+run bench_p1 "$P1" python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu --no-e2e --rows $ROWS || exit $?
+run bench_p2 "$P2" python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu --no-e2e --rows $ROWS || exit $?
 run dag_p1 "$P1" python3 $R/tools/dag_bench.py --steps 1 --rows $ROWS || exit $?
 run dag_p2 "$P2" python3 $R/tools/dag_bench.py --steps 1 --rows $ROWS || exit $?
 PBH_DAG=0 run pernode_p1 "$P1" python3 $R/tools/dag_bench.py --steps 1 --rows $ROWS || exit $?

@@ -1,11 +1,13 @@
 """Print the headline, the ppf sweep and the per-kernel tables of a bench.py JSON line
-(python tools/show_bench.py FILE)."""
+(python tools/show_bench.py FILE).  The roofline, the sweep and the standalone table are in the
+line of a `bench.py --full` run only."""
 import json
 import sys
 
 d = json.load(open(sys.argv[1]))
-print("value", d["value"], "Msamples/s  ms/step", d["ms_per_step"], " roofline", d["roofline"]["kernel"],
-      d["roofline"]["frac"], " pipeline", (d.get("pipeline_roofline") or {}).get("frac"))
+roof = d.get("roofline") or {}
+print("value", d["value"], "Msamples/s  ms/step", d["ms_per_step"], " roofline", roof.get("kernel"),
+      roof.get("frac"), " pipeline", (d.get("pipeline_roofline") or {}).get("frac"))
 sw = d.get("ppf_sweep")
 if sw:
     print("ppf sweep", sw["achieved"], "GB/s  frac", sw["frac"])
