@@ -17,7 +17,7 @@ def _corr(k, seed):
     return 0.8 * np.corrcoef(A, rowvar=False) + 0.2 * np.eye(k)
 
 
-@pytest.mark.parametrize("n,k", [(9, 2), (1000, 3), (20_000, 8), (4096, 32), (700, 40)])
+@pytest.mark.parametrize("n,k", [(9, 2), (1000, 3), (20_000, 8), (4096, 32), (700, 40), (1031, 65), (2051, 128)])
 def test_cholesky_matches_oracle(gpu, n, k):
     from oracle.correlators import cholesky_transform
     from probabilit_amd.correlation import Cholesky
@@ -72,7 +72,7 @@ def test_cholesky_validation(gpu):
 
 
 @pytest.mark.parametrize("remove_variance", [True, False])
-@pytest.mark.parametrize("n,k", [(3, 2), (500, 4), (10_000, 16)])
+@pytest.mark.parametrize("n,k", [(3, 2), (500, 4), (10_000, 16), (1031, 65), (1500, 128)])
 def test_decorrelate_matches_oracle(gpu, n, k, remove_variance):
     from oracle.correlators import decorrelate as ref_decorrelate
     from probabilit_amd.correlation import decorrelate

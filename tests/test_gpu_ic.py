@@ -6,6 +6,8 @@ correlation E within 1e-11 (different but exact-rounding reductions).  Golden ca
 from the reference run (tests/golden/ic.npz); larger N is checked against oracle.ic.
 """
 
+import functools
+
 import numpy as np
 import pytest
 import scipy.stats
@@ -57,20 +59,48 @@ def test_ic_doctest_statistics(gpu, icz):
     assert format(scipy.stats.pearsonr(*r.T).statistic, ".8f") == "0.27965287"
 
 
-@pytest.mark.parametrize("n,k", [(50_000, 3), (262_144, 32), (1_000_003, 8)])
-def test_ic_vs_oracle_bit_exact_indices(gpu, n, k):
+@functools.lru_cache(maxsize=1)
+def _oracle_case(n, k):
     from oracle import ic as oic
     from oracle.pipeline import cfg3_corr, cfg_dists, lhs_quantiles, ppf_columns
-    from probabilit_amd.correlation import ImanConover
 
     X = ppf_columns(lhs_quantiles(n, k, 7), cfg_dists(k))
     C = cfg3_corr(k)
-    ref = oic.iman_conover(X, C)
+    return X, C, oic.iman_conover(X, C)
+
+
+@pytest.mark.parametrize("n,k", [(50_000, 3), (262_144, 32), (1_000_003, 8), (2003, 33), (4099, 64), (4101, 65),
+                                 (3001, 127), (3002, 128)])
+def test_ic_vs_oracle_bit_exact_indices(gpu, n, k):
+    """Above K = 32 (the tile-pair Gram and the register kernel of step 3) E and CS are compared
+    as well, after checking that adjacent sorted CS values of the oracle are at least 1e-9 apart in
+    every column: far above the CS tolerance, so a last-bit difference cannot flip an index."""
+    from probabilit_amd.correlation import ImanConover
+
+    X, C, ref = _oracle_case(n, k)
+    if k > 32:
+        gap = float(np.diff(np.sort(ref["CS"], axis=0), axis=0).min())
+        assert gap >= 1e-9, f"smallest gap between sorted correlated scores {gap:.3g}"
     Y, S, CS, idx, E = ImanConover().set_target(C)._call_debug(X)
     mism = int((idx != ref["idx"]).sum())
     assert mism == 0, f"{mism} step-4 index mismatches"
     np.testing.assert_array_equal(Y, ref["Y"])
     assert_close(S, ref["S"], rtol=1e-14, atol=1e-300, what="scores")
+    if k > 32:
+        assert_close(E, ref["E"], rtol=1e-11, atol=1e-13, what="corrcoef")
+        assert_close(CS, ref["CS"], rtol=1e-11, atol=1e-12, what="correlated scores")
+
+
+def test_ic_block_call_above_32_odd_ld(gpu):
+    """The (K, N) block entry of the DAG path at (65, 4101): column stride 4101, odd."""
+    from probabilit_amd import device
+    from probabilit_amd.correlation import ImanConover
+
+    X, C, ref = _oracle_case(4101, 65)
+    block = device.to_device(np.ascontiguousarray(X.T))
+    assert block.stride(0) % 2 == 1
+    Y = ImanConover().set_target(C)._transform_device(block)
+    np.testing.assert_array_equal(device.to_host(Y).T, ref["Y"])
 
 
 @pytest.mark.parametrize("n,k", [(8_192, 2), (3_000_017, 4)])
