@@ -282,7 +282,7 @@ bool gen_dist_ok(int d) {
 }
 
 bool float_op_ok(int kind, int op) {  // the float64 operators of pbh_elementwise
-  if (kind == PBH_DAG_BINARY) return op >= PBH_OP_ADD && op <= PBH_OP_ARCTAN2;
+  if (kind == PBH_DAG_BINARY) return (op >= PBH_OP_ADD && op <= PBH_OP_MIN) || op == PBH_OP_ARCTAN2;
   return (op >= PBH_OP_NEG && op <= PBH_OP_ARCTANH) || op == PBH_OP_CAST;
 }
 

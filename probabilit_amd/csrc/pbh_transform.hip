@@ -225,9 +225,24 @@ struct AvgArgs {
 
 __global__ __launch_bounds__(kBlock) void k_average(AvgArgs args, int m, int64_t n, double* __restrict__ out,
                                                     int32_t* flag) {
+  // numpy adds the rows of the stacked parents into the result one after the other, except
+  // when there is a single column: that is one contiguous run, which it sums with eight
+  // accumulators (pairwise_sum's block for 8 <= m <= 128) and then the rest in order.
+  const bool one_run = n == 1 && m >= 8;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    double s = args.p[0][i];
-    for (int j = 1; j < m; ++j) s += args.p[j][i];
+    double s;
+    if (one_run) {
+      double r[8];
+      for (int k = 0; k < 8; ++k) r[k] = args.p[k][i];
+      int j = 8;
+      for (; j + 8 <= m; j += 8)
+        for (int k = 0; k < 8; ++k) r[k] += args.p[j + k][i];
+      s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+      for (; j < m; ++j) s += args.p[j][i];
+    } else {
+      s = args.p[0][i];
+      for (int j = 1; j < m; ++j) s += args.p[j][i];
+    }
     double x = s / (double)m;
     out[i] = x;
     flag_bits(flag, !isfinite(x), 1);

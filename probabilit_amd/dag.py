@@ -113,6 +113,8 @@ def _classify(plan, node, isns):
                 raise _Unfusable  # (reduce of one parent: that parent's own samples)
         if isinstance(node, BinaryTransform) and node.op_name not in _BINARY:
             raise _Unfusable
+        if isinstance(node, Avg) and n == 1 and len(node.parents) >= 8:
+            raise _Unfusable  # a single row: k_average sums it in numpy's pairwise order, not left to right
         vals = [plan.val[p][0] for p in node.get_parents()]
         if "none" in vals:
             raise _Unfusable  # NoOp's samples are None: arithmetic on it raises in the reference
