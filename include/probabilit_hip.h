@@ -276,6 +276,30 @@ int pbh_ppf(int dist, const double* q, int64_t q_stride, int64_t n, const pbh_pa
 int pbh_lhs_ppf(uint64_t seed, int64_t n, int64_t row0, int64_t nrows, int col, int dist,
                 const pbh_param* params, int nparams, double* out, int32_t* nonfinite_flag, void* stream);
 
+/* ---------------------------------------------------------------- multivariate samplers
+ * Distribution._sample's fallback for distributions without .ppf (modeling.py:806-812):
+ * scipy.stats.<name>(...).rvs(size=N, random_state=seed), seed = int(q[0] * 2**20).  The same law
+ * from a native stream (not numpy's MT19937 samplers): row r of the block is a function of the
+ * uniforms u(r, j) = pbh_fill_uniform(seed)'s element (r, j), j < d (u == 0 read as 2^-53), and of
+ * nothing else, so any row range [row0, row0 + nrows) is drawn independently.  out is column-major
+ * (d, ld), component c of row r at out[c * ld + (r - row0)], ld >= nrows; 1 <= d <= 128.  The
+ * parameter tables are host arrays.  One fused launch each: no workspace, no stored uniforms.
+ *
+ *   multivariate_normal  x = mean + A z, z_j = the norm ppf kernel's quantile of u_j; a_host the
+ *                        d x d row-major factor with A A^T = cov (V diag(sqrt(max(lambda, 0))) of
+ *                        eigh(cov)), float64 out
+ *   dirichlet            g_j = gammaincinv(alpha_j, u_j), x_j = g_j / sum_k g_k, float64 out; a row
+ *                        whose sum is 0 or non-finite sets the flag
+ *   multinomial          conditional binomials left to right: rem = n, x_j = binom(rem, pc_j).ppf(u_j)
+ *                        (0 once rem == 0), rem -= x_j, x_{d-1} = rem, with
+ *                        pc_j = clip(p_j / (1 - sum_{k<j} p_k), 0, 1) from the host; int64 out */
+int pbh_multivariate_normal(uint64_t seed, int64_t row0, int64_t nrows, int32_t d, const double* mean_host,
+                            const double* a_host, double* out, int64_t ld, int32_t* nonfinite_flag, void* stream);
+int pbh_dirichlet(uint64_t seed, int64_t row0, int64_t nrows, int32_t d, const double* alpha_host, double* out,
+                  int64_t ld, int32_t* nonfinite_flag, void* stream);
+int pbh_multinomial(uint64_t seed, int64_t row0, int64_t nrows, int32_t d, double n, const double* pc_host,
+                    int64_t* out, int64_t ld, int32_t* nonfinite_flag, void* stream);
+
 /* ---------------------------------------------------------------- Iman-Conover
  * ImanConover.__call__ (correlation.py:368-425) on device:
  *   step 1  ranks = rankdata(X, axis=0, 'average') / (N + 1); S = ndtri(ranks)     (:394-395)

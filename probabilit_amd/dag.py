@@ -294,8 +294,12 @@ def try_evaluate(order, isns, source, ev, gc):
     collector would leave them and returns True."""
     if not enabled():
         return False
-    from .modeling import Constant, NoOp, _Broadcast
+    from .modeling import _MULTIVARIATE, Constant, Distribution, MarginalDistribution, NoOp, _Broadcast
 
+    if any(isinstance(nd, MarginalDistribution) or (isinstance(nd, Distribution) and nd.distr in _MULTIVARIATE)
+           for nd in order):
+        counts["declined"] += 1  # a multivariate block is drawn by its own sampler (csrc/pbh_mvar.hip)
+        return False
     n = ev.size
     plan = plan_graph(order, isns, ev, gc)
     if plan is None:

@@ -245,7 +245,7 @@ class Node(abc.ABC):
         if dev is None:
             return None
         if d.get("_host") is None:
-            d["_host"] = dev.host() if isinstance(dev, _Broadcast) else device.to_host(dev)
+            d["_host"] = dev.host() if isinstance(dev, _Broadcast) else self._host_layout(device.to_host(dev))
         return d["_host"]
 
     @samples_.setter
@@ -271,6 +271,10 @@ class Node(abc.ABC):
     def _set_device(self, dev):
         self.__dict__["_smp"] = dev
         self.__dict__["_host"] = None
+
+    def _host_layout(self, host):
+        """`samples_` as the reference shapes it, from the downloaded device tensor."""
+        return host
 
     def _dev(self):
         return self.__dict__["_smp"]
@@ -363,6 +367,10 @@ class Node(abc.ABC):
         for var in variables:
             if var not in ancestors:
                 raise ValueError(f"{var} is not an ancestor of {self}")
+            if isinstance(var, MarginalDistribution) or (isinstance(var, Distribution) and var.distr in _MULTIVARIATE):
+                # a marginal is no initial sampling node, and a multivariate block has no single
+                # column for the correlator to reorder
+                raise ValueError(f"Cannot correlate variable: {var}")
         self._correlations.append((list(variables), np.copy(corr_mat)))
         return self
 
@@ -383,11 +391,13 @@ class Node(abc.ABC):
         d = self.num_distribution_nodes()
         if method is not None and method.lower().strip() not in ("lhs", "halton", "sobol"):
             raise KeyError(method.lower().strip())
+        self._prepare_multivariate()
         source = qmc.make_source(method, size, d, random_state, stream=stream)
         return self._evaluate(source, correlator, gc_strategy, to_host=True)
 
     def sample_from_quantiles(self, quantiles, correlator="imanconover", gc_strategy=None):
         """Evaluate the graph on given quantiles, shape (samples, dimensions) (modeling.py:495-614)."""
+        self._prepare_multivariate()
         src = qmc.DeviceMatrixSource(quantiles)
         return self._evaluate(src, correlator, gc_strategy, to_host=True)
 
@@ -401,8 +411,24 @@ class Node(abc.ABC):
         counter-addressed by the global row, correlations run through the row-sharded
         Iman-Conover of probabilit_amd.distributed."""
         size = 1 if size is None else size
+        self._prepare_multivariate(group)
         source = qmc.make_source(method, size, self.num_distribution_nodes(), random_state, stream=stream)
         return self._evaluate(source, correlator, gc_strategy, to_host=False, group=group)
+
+    def _prepare_multivariate(self, group=None):
+        """Validate the graph's multivariate distributions and prepare their host parameter tables
+        (scipy's own errors for a bad cov or p), before anything touches the device."""
+        nodes = [n for n in self._plan().all_nodes if isinstance(n, Distribution) and n.distr in _MULTIVARIATE]
+        if not nodes:
+            return
+        if group is not None:
+            import torch.distributed as tdist
+
+            if tdist.get_world_size(group) > 1:
+                raise NotImplementedError("a graph with a multivariate distribution is not row-sharded over a "
+                                          f"process group yet: {nodes[0]}")
+        for node in nodes:
+            node._multivariate_tables()
 
     def _evaluate(self, source, correlator, gc_strategy, to_host, group=None):
         plan = self._plan()
@@ -635,7 +661,7 @@ class Node(abc.ABC):
         pending = [nd for nd in set(self.nodes()) if "_smp" in nd.__dict__ and nd.__dict__.get("_host") is None
                    and nd.__dict__["_smp"] is not None and not isinstance(nd.__dict__["_smp"], _Broadcast)]
         for nd, host in zip(pending, device.to_host_many([nd.__dict__["_smp"] for nd in pending])):
-            nd.__dict__["_host"] = host
+            nd.__dict__["_host"] = nd._host_layout(host)
         return self.samples_
 
 
@@ -727,6 +753,9 @@ _DISCRETE = {"poisson", "binom", "bernoulli", "geom", "randint", "nbinom", "dlap
 # that Iman-Conover takes them as generated columns (pbh_ppf.hip k_lhs_sorted_ppf / k_place_gen;
 # the extended set pbh_ppf_ext.hip k_ext_sorted / k_ext_place): every distribution with a kernel
 _FUSED_LHS = set(_DIST_SHAPES)
+# distributions without a ppf: the reference draws them with .rvs seeded by the node's first
+# quantile (modeling.py:806-812); here one fused native sampler each (csrc/pbh_mvar.hip)
+_MULTIVARIATE = ("multivariate_normal", "dirichlet", "multinomial")
 
 
 def _parse_scipy_args(name, args, kwargs):
@@ -792,7 +821,47 @@ class Distribution(AbstractDistribution):
                           f"{np.asarray(vals[0])!r}.", RuntimeWarning, stacklevel=4)
         return [resolve(v) for v in vals]
 
+    def _multivariate_tables(self):
+        """Host parameter tables of a multivariate distribution, validated by constructing
+        scipy.stats.<name>(*args, **kwargs) once (no device call)."""
+        from . import native
+
+        for v in self.args + tuple(self.kwargs.values()):
+            if isinstance(v, Node):
+                raise NotImplementedError(f"{self.distr}: a Node as parameter has no device path (the parameter "
+                                          "tables of a multivariate distribution are prepared on the host)")
+        frozen = getattr(scipy.stats, self.distr)(*self.args, **self.kwargs)
+        _, tables = native.multivariate_tables(self.distr, frozen)
+        self.__dict__["_mv_tables"] = tables
+        return tables
+
+    def _sample_multivariate(self, ev, column):
+        """The (d, N) block of the fused sampler, its stream seeded by the node's first quantile as
+        the reference seeds .rvs: seed = int(q[0] * 2**20) (modeling.py:811)."""
+        from . import native
+
+        tables = self.__dict__.pop("_mv_tables", None) or self._multivariate_tables()
+        if column[0] == "lhs":  # one row of the native design
+            _, seed, n_total, col, _ = column
+            q = device.empty(1)
+            _lib.check(_lib.load().pbh_fill_lhs(seed, n_total, 0, 1, col, 1, q.data_ptr(), 1, device.stream()),
+                       "pbh_fill_lhs")
+        elif column[0] == "sobol":
+            q = column[1].materialize(column[2])
+        else:
+            q = column[1]
+        seed = int(float(q[0]) * 2**20)
+        return native.multivariate_launch(self.distr, tables, seed, ev.size, 0, ev.flag_ptr(self))
+
+    def _host_layout(self, host):
+        if self.distr in _MULTIVARIATE:  # the device block is (d, N); the reference's samples_ (N, d)
+            return np.ascontiguousarray(host.T)
+        return host
+
     def _sample_device(self, ev, column, out=None):
+        if self.distr in _MULTIVARIATE:
+            assert out is None  # (correlate() bars these nodes)
+            return self._sample_multivariate(ev, column)
         n = ev.size
         params = self._params(n)
         keep = [p for p in params if not isinstance(p, float)]  # keep vectors alive over the launch
@@ -1164,8 +1233,8 @@ def scalar_transform(func):
 
 
 class MarginalDistribution(Transform):
-    """Slice of a multivariate distribution (modeling.py:1215-1243); pseudo-random .rvs only
-    in the reference, so no inverse-CDF device path."""
+    """Slice of a multivariate distribution (modeling.py:1215-1243): row d of the parent's
+    (components, N) device block, as a view."""
 
     is_leaf = False
 
@@ -1175,7 +1244,7 @@ class MarginalDistribution(Transform):
         super().__init__()
 
     def _sample_device(self, ev):
-        raise NotImplementedError("multivariate distributions have no device path (SURVEY.md §2 #2)")
+        return self.distr._dev()[self.d]
 
     def get_parents(self):
         yield self.distr
@@ -1187,6 +1256,9 @@ class MarginalDistribution(Transform):
 def MultivariateDistribution(distr, *args, **kwargs):
     """Marginals of a multivariate scipy distribution (modeling.py:1246-1264)."""
     dist = Distribution(distr, *args, **kwargs)
+    if any(isinstance(v, Node) for v in args + tuple(kwargs.values())):
+        raise NotImplementedError(f"{distr}: a Node as parameter has no device path (the parameter tables of a "
+                                  "multivariate distribution are prepared on the host)")
     frozen = getattr(scipy.stats, distr)(*args, **kwargs)
     d = len(np.atleast_1d(frozen.rvs(size=1, random_state=0)).squeeze())
     yield from (MarginalDistribution(dist, d=i) for i in range(d))

@@ -72,6 +72,93 @@ def fill_uniform(seed, n, d, row0=0, return_device=False):
     return q if return_device else device.to_host(q).T
 
 
+MULTIVARIATE = ("multivariate_normal", "dirichlet", "multinomial")
+
+
+def mvn_factor(cov):
+    """A with A A^T = cov: V diag(sqrt(max(lambda, 0))) of np.linalg.eigh(cov) (what numpy's own
+    multivariate_normal factors a positive semi-definite cov by: rank-deficient ones included)."""
+    cov = np.atleast_2d(np.asarray(cov, dtype=np.float64))
+    lam, V = np.linalg.eigh(cov)
+    return np.ascontiguousarray(V * np.sqrt(np.maximum(lam, 0.0)))
+
+
+def multinomial_conditionals(p):
+    """pc_j = clip(p_j / (1 - sum_{k<j} p_k), 0, 1), the prefix sum left to right in float64: the
+    success probability of category j among the trials the categories before it left over (0 where
+    they left none)."""
+    p = np.asarray(p, dtype=np.float64).ravel()
+    left = 1.0 - np.concatenate([[0.0], np.cumsum(p)[:-1]])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pc = np.where(left > 0.0, p / left, 0.0)
+    return np.clip(pc, 0.0, 1.0)
+
+
+def multivariate_tables(name, frozen):
+    """The host parameter tables of the fused sampler of scipy.stats.<name>'s frozen distribution
+    (whose construction validated the arguments): (d, tables).  No device call."""
+    from .correlation import MAX_VARIABLES
+
+    if name == "multivariate_normal":
+        mean = np.ascontiguousarray(np.atleast_1d(frozen.mean), dtype=np.float64)
+        tables = (mean, mvn_factor(frozen.cov))
+    elif name == "dirichlet":
+        alpha = np.asarray(frozen.alpha, dtype=np.float64)
+        if alpha.ndim != 1:
+            raise NotImplementedError(f"dirichlet: alpha of shape {alpha.shape}; the device path takes one vector")
+        tables = (np.ascontiguousarray(alpha),)
+    elif name == "multinomial":
+        if np.ndim(frozen.n) != 0 or np.ndim(frozen.p) != 1:
+            raise NotImplementedError("multinomial: the device path takes a scalar n and one vector p, got shapes "
+                                      f"{np.shape(frozen.n)} and {np.shape(frozen.p)}")
+        if np.any(frozen.npcond):
+            raise ValueError("multinomial: n must be a non-negative integer and p probabilities that sum to 1")
+        tables = (float(frozen.n), multinomial_conditionals(frozen.p))
+    else:
+        raise NotImplementedError(name)
+    d = len(tables[-1])
+    if d > MAX_VARIABLES:
+        raise ValueError(f"probabilit_amd samples at most {MAX_VARIABLES} components of a multivariate "
+                         f"distribution on the device; got {d}")
+    return d, tables
+
+
+def multivariate_launch(name, tables, seed, n, row0, flag_ptr=None):
+    """The (d, n) device block of rows [row0, row0 + n) of the sampler's stream `seed`."""
+    lib = _lib.load()
+    d = len(tables[-1])
+    out = device.empty((d, n), "int64" if name == "multinomial" else "float64")
+    if name == "multivariate_normal":
+        mean, A = tables
+        st = lib.pbh_multivariate_normal(seed, row0, n, d, _lib.np_ptr(mean), _lib.np_ptr(A), out.data_ptr(), n,
+                                         flag_ptr, device.stream())
+    elif name == "dirichlet":
+        st = lib.pbh_dirichlet(seed, row0, n, d, _lib.np_ptr(tables[0]), out.data_ptr(), n, flag_ptr, device.stream())
+    else:
+        trials, pc = tables
+        st = lib.pbh_multinomial(seed, row0, n, d, trials, _lib.np_ptr(pc), out.data_ptr(), n, flag_ptr,
+                                 device.stream())
+    _lib.check(st, f"pbh_{name}")
+    return out
+
+
+def multivariate(name, seed, n, row0=0, return_device=False, **params):
+    """Rows [row0, row0 + n) of scipy.stats.<name>(**params) drawn by the fused native sampler from
+    the uniforms fill_uniform(seed, n, d, row0) (a native stream, not numpy's): (n, d) on the host or
+    (d, n) on the device.  n is the number of rows, as everywhere in this module; multinomial's
+    number of trials is passed as `trials`."""
+    import scipy.stats
+
+    if name not in MULTIVARIATE:
+        raise NotImplementedError(name)
+    if name == "multinomial" and "trials" in params:
+        params = dict(params, n=params["trials"])
+        del params["trials"]
+    _, tables = multivariate_tables(name, getattr(scipy.stats, name)(**params))
+    out = multivariate_launch(name, tables, seed, n, row0)
+    return out if return_device else device.to_host(out).T
+
+
 def fill_sobol(sv, shift, n, bits=30, row0=0, return_device=False):
     sv = np.ascontiguousarray(sv, dtype=np.uint32)
     shift = np.ascontiguousarray(shift, dtype=np.uint32)
