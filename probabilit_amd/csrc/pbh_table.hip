@@ -39,13 +39,14 @@ __device__ __forceinline__ int64_t upper_bound(const double* __restrict__ t, int
 
 __device__ __forceinline__ double interp_one(double x, const double* __restrict__ xp, const double* __restrict__ fp,
                                              int64_t m) {
+  if (m == 1) return fp[0];  // numpy's one-node loop compares only: a NaN x gets fp[0] too
   if (isnan(x)) return x;
-  if (m == 1) return fp[0];
   const double left = fp[0], right = fp[m - 1];
   if (x < xp[0]) return left;
   if (x > xp[m - 1]) return right;
   if (x == xp[m - 1]) return right;
   const int64_t j = upper_bound(xp, m, x) - 1;  // xp[j] <= x < xp[j + 1]
+  if (x == xp[j]) return fp[j];  // numpy returns the node's value before it forms a slope (fp[j + 1] = +-inf)
   const double slope = (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j]);
   double r = slope * (x - xp[j]) + fp[j];
   if (isnan(r)) {

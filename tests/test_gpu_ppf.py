@@ -141,9 +141,11 @@ def test_ppf_streaming_ragged_and_misaligned(gpu, name, kw):
 
 @pytest.mark.parametrize("kw", [{"a": 2.0}, {"a": 0.7, "scale": 3.0}, {"a": 0.05}, {"a": 45.0, "loc": 1.0}])
 def test_gamma_lds_table_bit_identical(gpu, kw):
-    """k_ppf_gamma_lds / k_lhs_ppf_gamma_lds (guide table staged in LDS; scalar parameters) give
-    the same bits as k_ppf / k_lhs_ppf reading the table from global memory (taken when loc is
-    a per-row vector, here all equal to the scalar) and as the stratum-ordered generator."""
+    """The scalar-parameter gamma sweep (by default k_ppf_gamma_w<LHS> with a window of the guide
+    table in LDS, followed by k_ppf_gamma_slow<LHS>; k_ppf_gamma_lds / k_lhs_ppf_gamma_lds run only
+    under PBH_GAMMA_WIN=0 and are tested in test_gpu_ppf_kernels.py) gives the same bits as k_ppf /
+    k_lhs_ppf reading the table from global memory (taken when loc is a per-row vector, here all
+    equal to the scalar) and as the stratum-ordered generator."""
     import ctypes
 
     from probabilit_amd import _lib, device, native

@@ -109,3 +109,45 @@ def test_sobol_dag_matches_materialised_quantiles(gpu):
     sv, shift = qmc.sobol_setup(3, 3)
     Q = native.fill_sobol(sv, shift, n)
     np.testing.assert_array_equal(y, model().sample_from_quantiles(Q))
+
+
+@pytest.mark.parametrize("col0", [0, 5, 17])
+@pytest.mark.parametrize("gen", ["lhs", "uniform", "sobol"])
+def test_generator_column_blocks(gpu, gen, col0):
+    """pbh_fill_lhs / pbh_fill_uniform / pbh_fill_sobol into a block of columns col0 .. col0 + ncols
+    with a leading dimension of nrows + 3: the block equals the same rows and columns of the full
+    (n, d) call (d = 33: three Sobol' launches of 16 columns), the three gap rows of every column
+    and the column after the last keep their sentinels, and so does everything around the block;
+    row0 = 0 and 777, nrows = 1 and 257."""
+    for row0 in (0, 777):
+        for nrows in (1, 257):
+            _column_block(gen, col0, row0, nrows)
+
+
+def _column_block(gen, col0, row0, nrows):
+    from abi_views import SENT, View
+    from probabilit_amd import _lib, device, native, qmc
+
+    d, bits, n_total, seed = 33, 30, 2000, 11
+    ncols, ldq = d - col0 - 1, nrows + 3
+    lib = _lib.load()
+    blk = View((ncols + 1) * ldq)
+    if gen == "lhs":
+        full = native.fill_lhs(seed, n_total, d, row0=row0, nrows=nrows)
+        st = lib.pbh_fill_lhs(seed, n_total, row0, nrows, col0, ncols, blk.ptr, ldq, device.stream())
+    elif gen == "uniform":
+        full = native.fill_uniform(seed, nrows, d, row0=row0)
+        st = lib.pbh_fill_uniform(seed, row0, nrows, col0, ncols, blk.ptr, ldq, device.stream())
+    else:
+        sv, shift = qmc.sobol_setup(d, seed)
+        svc, shc = np.ascontiguousarray(sv, np.uint32), np.ascontiguousarray(shift, np.uint32)
+        full = native.fill_sobol(sv, shift, nrows, bits=bits, row0=row0)
+        st = lib.pbh_fill_sobol(_lib.np_ptr(svc), _lib.np_ptr(shc), d, bits, row0, nrows, col0, ncols, blk.ptr, ldq,
+                                device.stream())
+    assert st == 0, _lib.last_error()
+    assert full.shape == (nrows, d)
+    got = blk.host(np.int64).reshape(ncols + 1, ldq)
+    np.testing.assert_array_equal(got[:ncols, :nrows].copy().view(np.float64).T, full[:, col0:col0 + ncols])
+    assert (got[:ncols, nrows:] == SENT).all(), "a gap row was written"
+    assert (got[ncols] == SENT).all(), "the column after the last was written"
+    assert blk.intact()
