@@ -640,6 +640,74 @@ int pbh_timing_read(int id, double* total_ms, int64_t* launches);
  * same non-temporal.  bench.py reports the fastest. */
 int pbh_hbm_copy(const void* src, void* dst, size_t bytes, int variant, void* stream);
 
+/* ---------------------------------------------------------------- summaries of samples
+ * What the reference's users do with node.samples_ afterwards, on the device: a handful of
+ * numbers per column instead of the column over PCIe.  X is a column-major block of k columns,
+ * column c at X + c * ld, n doubles each (the (d, N) block of a multivariate parent; k = 1 for one
+ * node's vector); columns need 8-byte alignment only.  The samples are only read; every workspace
+ * is independent of n. */
+#define PBH_SUMMARY_TILE 2048       /* samples per block tile of pbh_moments / pbh_histogram      */
+#define PBH_SUMMARY_MAX_BLOCKS 1024 /* blocks per column: the grid spans 2^21 samples per sweep   */
+#define PBH_MOMENTS_STRIDE 8        /* doubles per column of pbh_moments' output                  */
+#define PBH_SELECT_TILE 16384       /* keys per block tile of pbh_select_ranks                    */
+#define PBH_SELECT_MAX_BLOCKS 256
+#define PBH_SELECT_MAX_RANKS 64
+#define PBH_HISTOGRAM_MAX_BINS 4096
+
+/* np.isnan(x).sum(), np.min, np.max, np.mean and the central moments behind np.var / np.std (any
+ * ddof) and scipy.stats.skew / kurtosis (m_p = mean((x - mean)^p), p = 2, 3, 4, about the mean this
+ * call returns), per column: out[c * 8 + {0..6}] = nan count, min, max, mean, m2, m3, m4 (device;
+ * [7] is 0).  NaN propagates into min / max as in np.min; +-inf and NaN follow IEEE through the
+ * sums.  A column whose values are all equal has mean = that value, hence m2 = m3 = m4 = 0 exactly.
+ * Two reads of each sample, the mean first and then the centred sums, as np.var does.
+ *
+ * Summation shape (no atomics: the same bits on every run).  With tiles = ceil(n / 2048) and
+ * B = min(tiles, 1024) blocks per column, thread t of block b adds elements b' * 2048 + j * 256 + t
+ * (b' = b, b + B, ...; j = 0..7) serially in that order, the 256 threads of a block are summed by a
+ * binary tree of depth 8, and a second launch sums the B block partials: thread t adds partials
+ * t, t + 256, ... serially, then the same tree.  So every sum has
+ *     serial length L(n) = 8 * ceil(tiles / B) + ceil(B / 256),   tree depth D = 16,
+ * a term passes through at most L(n) + D additions and one division by n follows, each rounding
+ * once, by at most the unit roundoff u = 2^-53 relative.  A term of m_p also carries 2p - 1
+ * roundings of its own before it is added: with d = fl(x - mean) and d2 = fl(d * d) the terms are
+ * d2, fl(d2 * d) and fl(d2 * d2), in which the subtraction's rounding enters p times (once per
+ * factor d), d2's product once for p = 2 and 3 and twice for p = 4, and the last product once for
+ * p = 3 and 4: 3, 5 and 7 roundings (none for the mean's terms).  To first order the error is
+ * therefore (L(n) + D + 1) u mean(|x|) for the mean and (L(n) + D + 2p) u mean(|x - mean|^p) for
+ * m_p.  The a-priori bound is stated in eps = 2^-52 = 2u, which covers 2p - 1 <= 2p roundings per
+ * term and leaves a factor of two for the additions and the higher-order terms:
+ *     |mean - exact|  <= (L(n) + D + 1)     * eps * mean(|x|)
+ *     |m_p  - exact|  <= (L(n) + D + p + 1) * eps * mean(|x - mean|^p)
+ * ws >= pbh_moments_workspace_size(k) bytes of device memory. */
+int pbh_moments_workspace_size(int32_t k, size_t* bytes);
+int pbh_moments(const double* X, int64_t n, int32_t k, int64_t ld, double* out, void* ws, size_t ws_bytes,
+                void* stream);
+
+/* np.sort(x)[ranks] of one column without sorting it: m <= 64 zero-based ranks (host; any order,
+ * repeats allowed), values to out_host.  Ordering is np.sort's: by the order-preserving 64-bit image
+ * of the doubles (-0.0 == +0.0, returned as +0.0), every NaN last.  Multi-target radix select, four
+ * passes over 16-bit digits from the top: pass p counts, for every key whose top 16 p bits equal
+ * some target's, the next digit into that prefix' 65536 counters; a one-block-per-target kernel
+ * then finds each target's digit and remaining rank, read back with one synchronisation per pass.
+ * Four reads of the column whatever the data (equal keys included), no write proportional to n,
+ * no fallback.  n < 2^32.  ws >= pbh_select_workspace_size(m) bytes.  Synchronises the stream. */
+int pbh_select_workspace_size(int32_t m, size_t* bytes);
+int pbh_select_ranks(const double* x, int64_t n, const int64_t* ranks_host, int32_t m, double* out_host, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* np.histogram(x, bins=B, range=(edges[0], edges[B]))[0] per column for the B + 1 uniform edges
+ * np.linspace(lo, hi, B + 1) (host), 1 <= B <= 4096: counts[c * B + i] (device int64) = the
+ * number of edges[i] <= x < edges[i + 1], the last bin closed; values outside and NaN are not
+ * counted.  The bin is guessed by one multiply and corrected against the edge table in LDS
+ * (numpy lib/_histograms_impl.py does the same against its linspace edges), so the counts are
+ * numpy's.  One read of each sample.  ws >= pbh_histogram_workspace_size(B) bytes.  The call
+ * returns without synchronising: the edges are uploaded by an asynchronous copy on `stream`, so
+ * edges_host must stay valid and unchanged until the stream has passed this call (a
+ * synchronisation of the stream, or of the read-back of counts). */
+int pbh_histogram_workspace_size(int32_t bins, size_t* bytes);
+int pbh_histogram(const double* X, int64_t n, int32_t k, int64_t ld, const double* edges_host, int32_t bins,
+                  int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

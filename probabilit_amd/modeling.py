@@ -252,6 +252,7 @@ class Node(abc.ABC):
     def samples_(self, value):
         self.__dict__["_smp"] = _to_device_samples(value)
         self.__dict__["_host"] = value if isinstance(value, np.ndarray) else None
+        self.__dict__.pop("_shard", None)
 
     @samples_.deleter
     def samples_(self):
@@ -259,6 +260,7 @@ class Node(abc.ABC):
             raise AttributeError("samples_")
         del self.__dict__["_smp"]
         self.__dict__.pop("_host", None)
+        self.__dict__.pop("_shard", None)
 
     @property
     def samples_device(self):
@@ -271,6 +273,7 @@ class Node(abc.ABC):
     def _set_device(self, dev):
         self.__dict__["_smp"] = dev
         self.__dict__["_host"] = None
+        self.__dict__.pop("_shard", None)
 
     def _host_layout(self, host):
         """`samples_` as the reference shapes it, from the downloaded device tensor."""
@@ -654,6 +657,10 @@ class Node(abc.ABC):
                     shown = node.samples_ if "_smp" in node.__dict__ else "(garbage collected)"
                     raise ValueError(f"Sampling this node gave non-finite values: {node}\n{shown}")
 
+        if world > 1:  # each node holds this rank's rows only (probabilit_amd.inspection declines them)
+            for node in all_nodes:
+                if "_smp" in node.__dict__:
+                    node.__dict__["_shard"] = (rank, world)
         if not to_host:
             return None if self._dev() is None else self.samples_device
         # the reference leaves numpy samples_ on every node (modeling.py:582-583, 598, 614): hand

@@ -169,6 +169,88 @@ def fill_sobol(sv, shift, n, bits=30, row0=0, return_device=False):
     return q if return_device else device.to_host(q).T
 
 
+# launch shapes of the summary kernels (include/probabilit_hip.h): a block's tile and the samples
+# one sweep of the whole grid spans
+SUMMARY_TILE, SUMMARY_SPAN = 2048, 2048 * 1024
+SELECT_TILE, SELECT_SPAN = 16384, 16384 * 256
+SELECT_MAX_RANKS = 64
+HISTOGRAM_MAX_BINS = 4096
+MOMENT_FIELDS = ("nan", "min", "max", "mean", "m2", "m3", "m4")
+
+
+def moments_terms(n):
+    """(serial length L(n), tree depth D) of every sum pbh_moments forms over n samples: the
+    summation shape stated beside its declaration, from which a caller bounds the rounding error."""
+    tiles = -(-n // SUMMARY_TILE)
+    blocks = min(tiles, SUMMARY_SPAN // SUMMARY_TILE)
+    return 8 * -(-tiles // blocks) + -(-blocks // 256), 16
+
+
+def _block(x_dev):
+    """(k, n, ld) of a device float64 vector or (k, n) block whose rows are contiguous."""
+    import torch
+
+    if not isinstance(x_dev, torch.Tensor) or x_dev.dtype != torch.float64 or x_dev.dim() not in (1, 2):
+        raise TypeError("a float64 device vector or (k, n) block is required")
+    if x_dev.stride(-1) != 1 and x_dev.shape[-1] > 1:
+        raise ValueError("the samples of a column must be contiguous")
+    if x_dev.dim() == 1:
+        return 1, x_dev.shape[0], x_dev.shape[0]
+    return x_dev.shape[0], x_dev.shape[1], (x_dev.stride(0) if x_dev.shape[0] > 1 else x_dev.shape[1])
+
+
+def _workspace(query, arg):
+    import ctypes
+
+    b = ctypes.c_size_t()
+    _lib.check(query(arg, ctypes.byref(b)))
+    return device.empty(b.value, "uint8"), b.value
+
+
+def moments(x_dev):
+    """(k, 7) host array of MOMENT_FIELDS per column of a device vector / (k, n) block (pbh_moments)."""
+    lib = _lib.load()
+    k, n, ld = _block(x_dev)
+    ws, nbytes = _workspace(lib.pbh_moments_workspace_size, k)
+    out = device.empty((k, 8))
+    _lib.check(lib.pbh_moments(x_dev.data_ptr(), n, k, ld, out.data_ptr(), ws.data_ptr(), nbytes, device.stream()),
+               "pbh_moments")
+    return device.to_host(out)[:, :7]
+
+
+def select_ranks(x_dev, ranks):
+    """np.sort(x)[ranks] of one device vector for at most SELECT_MAX_RANKS ranks (pbh_select_ranks)."""
+    lib = _lib.load()
+    k, n, _ = _block(x_dev)
+    if k != 1:
+        raise ValueError("select_ranks takes one column")
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+    out = np.empty(len(ranks), dtype=np.float64)
+    if len(ranks) == 0:
+        return out
+    ws, nbytes = _workspace(lib.pbh_select_workspace_size, len(ranks))
+    _lib.check(lib.pbh_select_ranks(x_dev.data_ptr(), n, _lib.np_ptr(ranks), len(ranks), _lib.np_ptr(out),
+                                    ws.data_ptr(), nbytes, device.stream()), "pbh_select_ranks")
+    return out
+
+
+def histogram(x_dev, bins, range):
+    """(counts, edges): np.histogram(x, bins, range) per column of a device vector / (k, n) block for
+    an integer `bins` and a finite (lo, hi); counts is (bins,) for a vector, else (k, bins)."""
+    lib = _lib.load()
+    k, n, ld = _block(x_dev)
+    lo, hi = (float(v) for v in range)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"histogram: the range [{lo}, {hi}] is not finite and increasing")
+    edges = np.linspace(lo, hi, int(bins) + 1)
+    ws, nbytes = _workspace(lib.pbh_histogram_workspace_size, int(bins))
+    counts = device.empty((k, int(bins)), "int64")
+    _lib.check(lib.pbh_histogram(x_dev.data_ptr(), n, k, ld, _lib.np_ptr(edges), int(bins), counts.data_ptr(),
+                                 ws.data_ptr(), nbytes, device.stream()), "pbh_histogram")
+    host = device.to_host(counts)
+    return (host[0] if x_dev.dim() == 1 else host), edges
+
+
 def transpose(x_dev, rows, cols):
     out = device.empty((cols, rows))
     _lib.check(_lib.load().pbh_transpose(x_dev.data_ptr(), rows, cols, cols, out.data_ptr(), rows,
