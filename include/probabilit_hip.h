@@ -374,7 +374,10 @@ int pbh_lhs_sorted_ppf(uint64_t seed, int64_t n, int64_t t0, int64_t nt, int col
  * device u32, hcap entries): the run heads -- every t in (t0, t0 + nt) whose value differs from
  * stratum t - 1's, plus t0 itself when t0 == 0 -- unordered, at most hcap written; *hcur_dev
  * (device u32) counts them all.  A shard starting at row0 > 0 passes t0 = row0 - 1, so that the
- * pair across the shard boundary is counted exactly once.  certify != 0 (continuous columns,
+ * pair across the shard boundary is counted exactly once, and over the shards no head is
+ * reported twice -- except by a shard that starts at row0 == 1: its t0 is 0 as well, so stratum 0
+ * comes from it and from the first shard (pbh_lhs_scores takes a sorted list that starts 0, 0:
+ * the empty run changes no rank).  certify != 0 (continuous columns,
  * no heads): the tie / inversion certificate instead of the counts -- the inverse CDF evaluated
  * only at the pairs whose quantile gap its error bound could close (see pbh_ppf.hip); counts
  * then read non-zero unless the segment is certified free of ties and inversions, and a caller

@@ -849,11 +849,13 @@ __global__ __launch_bounds__(kGBlock) void k_place_gen_gamma(const uint64_t* __r
     for (int j = 0; j < kPer; ++j) {
       const bool valid = pr[j] != ~0ull;
       const double q = lhs_sorted_quantile(ph, (uint64_t)(uint32_t)pr[j], col, (uint64_t)n);
-      // igami_guided's interpolation branch, operation for operation
+      // igami_guided's interpolation branch, operation for operation (its log-odds too: with
+      // log_tab of the ratio instead, w moved by an ulp and the value by up to 53 ulp from the
+      // sorted column's; the guide leaves no LDS for the log table, so the global one as there)
       bool fast = valid && cond0 && q > 0.0 && q < 1.0;
       double v = 0.0;
       if (fast) {
-        const double w = sf::log_tab(q / (1.0 - q));
+        const double w = sf::log_odds_at(q, &sf::pbh_log_tab[0][0]);
         const double u = (w - T.z0) * T.inv_h;
         fast = u >= 0.0 && u < (double)(T.m - 1);
         if (fast) {
