@@ -445,8 +445,8 @@ int pbh_ic_column_scores(const double* x, int64_t stride, int64_t n, double* sco
  *                         host synchronisation.  cs, y / p_out must stay valid until
  *                         pbh_ic_owned_finish returns.
  *   pbh_ic_owned_finish   the caller's stream joins the lanes; one readback of every column's
- *                         verdict; a column the fast passes rejected (spiky codes, runs of equal
- *                         codes beyond the finish) is redone by the general path, redone_host[i]
+ *                         verdict; a column the fast passes rejected (spiky codes, a bin of
+ *                         more than 32 items in the finish) is redone by the general path, redone_host[i]
  *                         = 1 for it (its y changed after done_event).  Synchronises `stream`.
  *   pbh_ic_owned_destroy  frees the tables (after the lanes).
  * Calls on one device are not concurrent (one host thread per device). */
@@ -457,6 +457,18 @@ int pbh_ic_owned_create(const pbh_ic_column* columns, int32_t m, int64_t n, void
 int pbh_ic_owned_column(pbh_ic_owned* h, int32_t i, const double* cs, double* y, int64_t y_rs, uint32_t* p_out,
                         void* ready_event, void* done_event, void* stream);
 int pbh_ic_owned_finish(pbh_ic_owned* h, int32_t* redone_host, void* stream);
+/* Read-only: why the fast passes kept or rejected the launched column i, for tests and diagnosis.
+ * After pbh_ic_owned_finish (which leaves these device words as the passes wrote them) and before
+ * pbh_ic_owned_destroy; the outputs are host words; synchronises the device.
+ *   state  bit 0: a packed 16-bit counter of the top-16 histogram saturated in one block;
+ *          bit 1: a top-16 bucket holds more than 2048 items.  After the adaptive re-code: of
+ *          the second count.
+ *   flags  bit 0: a bin of the bucket finish (32 adjacent codes) holds more than 32 items;
+ *          bit 2: the column is not flat (state != 0) after the adaptive code map.
+ *   retry  1 when the column was re-coded with the adaptive code map (state != 0 at the first
+ *          count), else 0.
+ * redone_host[i] of pbh_ic_owned_finish = (state != 0 || flags != 0). */
+int pbh_ic_owned_verdict(pbh_ic_owned* h, int32_t i, int32_t* state, int32_t* flags, int32_t* retry);
 int pbh_ic_owned_destroy(pbh_ic_owned* h, void* stream);
 /* Every uncorrelated native-LHS leaf of a graph in one call (the per-node loop of
  * Node.sample_from_quantiles, modeling.py:529-538, for leaf Distributions with scalar parameters):

@@ -951,6 +951,16 @@ extern "C" int pbh_ic_owned_finish(pbh_ic_owned* h, int32_t* redone_host, void* 
   return PBH_OK;
 }
 
+extern "C" int pbh_ic_owned_verdict(pbh_ic_owned* h, int32_t i, int32_t* state, int32_t* flags, int32_t* retry) {
+  PBH_REQUIRE(h && state && flags && retry && i >= 0 && i < h->m, "pbh_ic_owned_verdict: bad arguments");
+  // finish() joined the lanes and left the three words as the passes wrote them
+  PBH_CHECK_HIP(hipMemcpy(state, h->sh.state + i, 4, hipMemcpyDeviceToHost));
+  PBH_CHECK_HIP(hipMemcpy(flags, h->sh.flags + i, 4, hipMemcpyDeviceToHost));
+  PBH_CHECK_HIP(hipMemcpy(retry, h->sh.retry + i, 4, hipMemcpyDeviceToHost));
+  PBH_CHECK_HIP(hipDeviceSynchronize());
+  return PBH_OK;
+}
+
 extern "C" int pbh_ic_owned_destroy(pbh_ic_owned* h, void* stream) {
   if (!h) return PBH_OK;
   hipStream_t s = as_stream(stream);

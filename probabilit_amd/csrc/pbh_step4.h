@@ -11,9 +11,9 @@ constexpr int kGenPlaceShift = 12;  // final placement blocks of 4096 rows (32 K
 
 // per-call state of all k columns (device): histograms, bucket starts, cursors, tile maps,
 // state[c] (bit 0 counter overflow, bit 1 bucket above the finish capacity: the column is not
-// flat) and flags[c] (bit 0: a run of equal codes too long for the finish; bit 2: the column is
-// still not flat after the adaptive code map -- every later pass skips it, and it is redone by
-// the general path after the others).  A column that is not flat under the fixed N(0, 1) code
+// flat) and flags[c] (bit 0: a bin of the finish, 32 adjacent codes, holds more than kBinCap =
+// 32 items; bit 2: the column is still not flat after the adaptive code map -- every later pass
+// skips it, and it is redone by the general path after the others).  A column that is not flat under the fixed N(0, 1) code
 // map (a score dominated by a discrete column: a mixture of narrow peaks) is re-coded once with
 // a code map built from its own histogram (retry[c] = 1; seghist, amap) and re-counted.
 constexpr int kAdaptSegments = 4096;  // adaptive code map: segments of [-8.5, 8.5]

@@ -7,9 +7,10 @@
 //            start of every top-16 bucket, a per-column flatness check        (read 4 B)
 //   msd1     (code, row) scattered by the top code byte                       (read 4, write 8)
 //   msd2     (low 16 code bits, row) scattered into the top-16 buckets        (read 8, write 6)
-//   finish   one wave per bucket (~1500 items): sort by the low 16 bits in LDS, order runs of
-//            equal codes by the full CS value (exact ties flagged), emit (row, p') packed in a
-//            u64 with p' = the sorted position, or the tie group's 'average' position  (read 6, write 8)
+//   finish   two buckets per block (~1500 items each): count the items into bins of 32 adjacent
+//            codes in LDS, rank every item inside its bin (equal codes by the full CS value), emit
+//            (row, p') packed in a u64 with p' = the sorted position, or the tie group's
+//            'average' position                                                (read 6, write 8)
 //   place    MSD passes on the row of (row, p') until every 4096-row block is together (read 8,
 //            write 8 per pass; 2 passes at N = 1e8), then gen_place assembles each block in
 //            LDS, regenerating sort(X)[p'] (write 8)
@@ -18,8 +19,8 @@
 // (tile, digit): no decoupled look-back, no status words, no host round trip.  Stability is not
 // needed anywhere: the bucket finish orders every bucket completely, and the row placement
 // writes each value at its own row.  Host decisions are batched: one readback after hist16 for
-// all columns (flatness), one at the end (buckets that met a run longer than kRunCap), whose
-// columns are redone by the general path (pbh_phases.hip reorder_column).
+// all columns (flatness), one at the end (buckets that met a bin of more than kBinCap = 32
+// items), whose columns are redone by the general path (pbh_phases.hip reorder_column).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,8 +38,7 @@ namespace {
 constexpr int kT = 256;
 constexpr int kIptP = 16;
 constexpr int kTileP = kT * kIptP;  // placement tiles: 4096 pairs (divides every group size 2^s >= 2^12)
-constexpr int kBucketCap2 = 2048;   // items per top-16 bucket a wave can finish
-constexpr int kRunCap = 16;         // longest run of equal codes the finish orders
+constexpr int kBucketCap2 = 2048;   // items per top-16 bucket a block can finish
 // Cursor spacing (u32 words) of the code-pass and finish cursors: one 64-byte line each.
 static int cur_pad() { return 16; }
 
@@ -977,7 +977,7 @@ void step4_gen_carve_shared(void* ws, int k, Step4Shared& sh) {
   p += (size_t)k * kAdaptMapWords * 4;
   p = (char*)(((uintptr_t)p + 63) & ~(uintptr_t)63);
   sh.state = (int32_t*)p;   // k words: bit 0 counter overflow, bit 1 bucket over cap
-  sh.flags = sh.state + k;  // k words: bit 0 long run / too many runs in a bucket, bit 2 not flat
+  sh.flags = sh.state + k;  // k words: bit 0 a bin above kBinCap items in the finish, bit 2 not flat
   sh.retry = sh.flags + k;  // k words: re-coded with the adaptive map
 }
 

@@ -74,8 +74,8 @@ def test_generated_step4_exact_ties(gpu, n):
     """poisson(mu=1e5) in the leading column: its van der Waerden scores tie in small groups
     (each k holds ~2-3 of 3000 draws), so column 0's correlated scores tie exactly and step 4
     takes the 'average' rank of every tie group (idx = int(avg) - 1 shared by the group).  At
-    n = 30000 the groups (~25-40 equal codes) exceed the finish's run capacity: the column is
-    flagged and redone by the general path."""
+    n = 30000 the groups (~25-40 equal codes) fill bins of the finish beyond its capacity of 32
+    items (kBinCap): the column is flagged and redone by the general path."""
     dists = [("poisson", {"mu": 1e5}), ("norm", {}), ("gamma", {"a": 2.0})]
     C = np.array([[1.0, 0.5, 0.2], [0.5, 1.0, 0.3], [0.2, 0.3, 1.0]])
     Y, idx = _run(n, dists, 9, C)
@@ -86,9 +86,9 @@ def test_generated_step4_exact_ties(gpu, n):
 
 
 def test_generated_step4_long_runs_fall_back(gpu):
-    """poisson(mu=4) leading: its scores tie in runs of thousands, so the bucket finish flags
-    the column (runs longer than 16 equal codes) and it is redone by the general path; the
-    result still equals the oracle's."""
+    """poisson(mu=4) leading: its scores tie in runs of thousands, far beyond the 32 items a bin
+    of the bucket finish holds (kBinCap) and the 2048 of a bucket, so the fast passes reject the
+    column and it is redone by the general path; the result still equals the oracle's."""
     dists = [("poisson", {"mu": 4.0}), ("norm", {}), ("triang", {"c": 0.3})]
     C = np.array([[1.0, 0.4, 0.1], [0.4, 1.0, 0.2], [0.1, 0.2, 1.0]])
     n = 200_000
