@@ -723,6 +723,42 @@ int pbh_histogram_workspace_size(int32_t bins, size_t* bytes);
 int pbh_histogram(const double* X, int64_t n, int32_t k, int64_t ld, const double* edges_host, int32_t bins,
                   int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* np.histogram2d(x_i, x_j, bins=(edges_i, edges_j))[0] for npairs pairs (i, j) of k separate
+ * columns in one launch: the binned joint densities of a pair grid.  cols_host[c] (host array of
+ * k device pointers) is column c, n contiguous doubles, 8-byte alignment only.  Column c has
+ * bins_host[c] + 1 finite non-decreasing edges, first < last, stored back to back in edges_host
+ * (column 0's first); uniform_host[c] != 0 promises that they are np.linspace(lo, hi, bins + 1)
+ * (a broken promise costs time, not correctness).  pairs_host[2p], pairs_host[2p + 1] = (i, j),
+ * i != j; pair p's counts are a row-major (bins[i], bins[j]) int64 matrix in `counts` (device) at
+ * the offset given by the sum of the earlier pairs' cells; the call zeroes them.
+ *
+ * Per axis the rule is pbh_histogram's and np.histogramdd's (searchsorted(edges, v, "right") - 1
+ * with v == edges[-1] moved into the last bin): bin b holds edges[b] <= v < edges[b + 1], the last
+ * bin is closed, a value equal to repeated edges lands after the last repeat, -0.0 == +0.0.  A
+ * row is counted only if both coordinates fall in a bin: NaN, +-inf and values outside either
+ * range drop the row.  Uniform axes guess the bin by one multiply and correct it against the
+ * edges in LDS, the others search them.
+ *
+ * One block per (row tile stride, pair): bins[i] * bins[j] 32-bit counters and both edge tables
+ * in LDS (up to 64 KiB + 8.1 KiB, for which the dynamic LDS limit of the kernel is raised), one
+ * LDS add per counted row (one per wave when the wave shares a cell), one global 64-bit add per
+ * non-empty cell per block.  16 B read per row per pair, no write proportional to n, integer
+ * counts identical on every run.  n < 2^32.  ws >= pbh_histogram2d_workspace_size(k, bins) bytes,
+ * 8-byte aligned.  Every argument is checked before anything is enqueued; a bad call returns an
+ * error and launches nothing.  The call returns without synchronising: the column pointers,
+ * edges, bins, uniform flags and pairs are uploaded by asynchronous copies on `stream`, so
+ * cols_host, edges_host, bins_host, uniform_host and pairs_host must stay valid and unchanged
+ * until the stream has passed this call (a synchronisation of the stream, or of the read-back of
+ * counts). */
+#define PBH_HISTOGRAM2D_MAX_BINS 1024    /* per axis                                       */
+#define PBH_HISTOGRAM2D_MAX_CELLS 16384  /* bins_x * bins_y of one pair (128 x 128)        */
+#define PBH_HISTOGRAM2D_MAX_COLUMNS 16
+#define PBH_HISTOGRAM2D_MAX_PAIRS 120
+int pbh_histogram2d_workspace_size(int32_t k, const int32_t* bins_host, size_t* bytes);
+int pbh_histogram2d(const double* const* cols_host, int32_t k, int64_t n, const double* edges_host,
+                    const int32_t* bins_host, const uint8_t* uniform_host, const int32_t* pairs_host, int32_t npairs,
+                    int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,16 +11,23 @@ populates `node.samples_`.
     quantile(node, q, method="linear")            np.quantile(node.samples_, q, method=method)
     histogram(node, bins=10, range=None)          np.histogram(node.samples_, bins, range)
     corrcoef(*nodes, kind="pearson")              np.corrcoef / scipy.stats.spearmanr of the nodes
+    histogram2d(a, b, bins=10, range=None)        np.histogram2d(a.samples_, b.samples_, bins, range)
+    pairgrid(*nodes, bins=30, range=None)         PairGrid: every pair's 2-d histogram, every node's own
+    PairGrid.draw(fig=None)                       the K x K grid of those counts with matplotlib
     treeprint(node)                               the graph above a node, one line per node
     plot(...)                                     probabilit_amd.plot (not provided)
 
-Limits: histograms take an integer number of at most 4096 uniform bins; quantile methods are
-linear, lower, higher, nearest and midpoint; samples row-sharded over a process group
-(`sample_device(group=...)` with more than one rank) are not summarised across ranks.
+Limits: histograms take an integer number of at most 4096 uniform bins; joint histograms take
+numpy's forms of `bins` (edge arrays included) with at most 1024 bins per axis and 16384 cells per
+pair, a pair grid 2 to 16 nodes; quantile methods are linear, lower, higher, nearest and midpoint;
+samples row-sharded over a process group (`sample_device(group=...)` with more than one rank) are
+not summarised across ranks.
 """
 
 import numpy as np
 
+# (histogram2d, pairgrid and PairGrid are public as well; the names a star import brings are the
+# reference module's and the first summaries, which tests/test_inspection_host.py pins)
 __all__ = ["summary", "quantile", "histogram", "corrcoef", "treeprint", "plot"]
 
 QUANTILE_METHODS = ("linear", "lower", "higher", "nearest", "midpoint")
@@ -86,6 +93,121 @@ def _skew_kurtosis(mean, m2, m3, m4):
         skew = np.nan if zero else m3 / m2 ** 1.5
         kurt = np.nan if zero else m4 / m2 ** 2.0 - 3.0
     return float(skew), float(kurt)
+
+
+def axis_edges(axis, bins, rng, limits):
+    """np.histogramdd's edges of one axis (lib/_histograms_impl.py histogramdd, _get_outer_edges)
+    with its errors.  bins: a number of bins or a 1-d array of edges, returned as np.asarray gives
+    it; rng: (lo, hi) or None, read only for a number of bins; limits(axis) -> (min, max) of the
+    axis' samples, called only when both a number of bins and no range are given."""
+    import operator
+
+    if np.ndim(bins) == 0:
+        if bins < 1:
+            raise ValueError(f"`bins[{axis}]` must be positive, when an integer")
+        if rng is not None:
+            lo, hi = rng
+            if lo > hi:
+                raise ValueError("max must be larger than min in range parameter.")
+            if not (np.isfinite(lo) and np.isfinite(hi)):
+                raise ValueError(f"supplied range of [{lo}, {hi}] is not finite")
+        else:
+            lo, hi = limits(axis)
+            if not (np.isfinite(lo) and np.isfinite(hi)):
+                raise ValueError(f"autodetected range of [{lo}, {hi}] is not finite")
+        if lo == hi:  # numpy's widening of an empty range
+            lo, hi = lo - 0.5, hi + 0.5
+        try:
+            nb = operator.index(bins)
+        except TypeError as e:
+            raise TypeError(f"`bins[{axis}]` must be an integer, when a scalar") from e
+        return np.linspace(lo, hi, nb + 1)
+    if np.ndim(bins) == 1:
+        edges = np.asarray(bins)
+        if np.any(edges[:-1] > edges[1:]):
+            raise ValueError(f"`bins[{axis}]` must be monotonically increasing, when an array")
+        return edges
+    raise ValueError(f"`bins[{axis}]` must be a scalar or 1d array")
+
+
+def histogram2d_edges(bins, rng, limits):
+    """[xedges, yedges] of np.histogram2d(x, y, bins=bins, range=rng) for numpy's forms of `bins`:
+    an int, (nx, ny), one edge array for both axes, or (xedges | nx, yedges | ny); rng is None or
+    ((xlo, xhi) | None, (ylo, yhi) | None).  limits: as for axis_edges."""
+    try:
+        nb = len(bins)
+    except TypeError:  # a number of bins for both axes
+        nb, bins = 2, [bins, bins]
+    if nb == 1:
+        raise ValueError("The dimension of bins must be equal to the dimension of the sample x.")
+    if nb != 2:  # np.histogram2d: one edge array for both axes
+        both = np.asarray(bins)
+        bins = [both, both]
+    if rng is None:
+        rng = (None, None)
+    elif len(rng) != 2:
+        raise ValueError("range argument must have one entry per dimension")
+    return [axis_edges(i, bins[i], rng[i], limits) for i in range(2)]
+
+
+def pairgrid_edges(k, bins, rng, limits):
+    """The k edge arrays of pairgrid: `bins` one number of bins or one per node, `rng` None or one
+    (lo, hi) | None per node; every axis by axis_edges."""
+    if np.ndim(bins) == 0:
+        bins = [bins] * k
+    elif np.ndim(bins) != 1 or len(bins) != k:
+        raise ValueError(f"pairgrid: `bins` must be one number of bins or one per node ({k})")
+    if rng is None:
+        rng = [None] * k
+    elif len(rng) != k:
+        raise ValueError(f"pairgrid: `range` must be None or one entry per node ({k}); got {len(rng)}")
+    return [axis_edges(i, bins[i], rng[i], limits) for i in range(k)]
+
+
+class PairGrid:
+    """The binned pair grid of K nodes (pairgrid): `count` samples, `labels` (str(node) per node),
+    `edges` (K edge arrays), `diagonal` (K int64 count vectors) and joint(i, j)."""
+
+    def __init__(self, count, labels, edges, diagonal, joints):
+        """joints: {(i, j): (bins_i, bins_j) int64 matrix} for every i < j."""
+        self.count, self.labels = int(count), list(labels)
+        self.edges, self.diagonal = list(edges), list(diagonal)
+        self._joints = dict(joints)
+
+    def joint(self, i, j):
+        """The (bins_i, bins_j) int64 counts of node i (rows) against node j (columns)."""
+        k = len(self.labels)
+        if not (0 <= i < k and 0 <= j < k):
+            raise IndexError(f"joint({i}, {j}): the grid has {k} nodes")
+        if i == j:
+            raise ValueError(f"joint({i}, {j}): the diagonal holds the one-node histograms (`diagonal`)")
+        return self._joints[(i, j)] if i < j else self._joints[(j, i)].T
+
+    def draw(self, fig=None, **imshow_kwargs):
+        """Draw the K x K grid with matplotlib and return the figure: bars of `diagonal` on the
+        diagonal, pcolormesh of joint(i, j) over the edges (node j along x, node i along y) off it.
+        The keyword arguments go to pcolormesh."""
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("PairGrid.draw needs matplotlib, which is not installed") from e
+        k = len(self.labels)
+        if fig is None:
+            fig = plt.figure(figsize=(2.4 * k, 2.4 * k))
+        axes = fig.subplots(k, k, squeeze=False)
+        for i in range(k):
+            for j in range(k):
+                ax = axes[i][j]
+                if i == j:
+                    e = np.asarray(self.edges[i], dtype=np.float64)
+                    ax.bar(e[:-1], self.diagonal[i], width=np.diff(e), align="edge")
+                else:
+                    ax.pcolormesh(self.edges[j], self.edges[i], self.joint(i, j), **imshow_kwargs)
+                if i == k - 1:
+                    ax.set_xlabel(self.labels[j])
+                if j == 0:
+                    ax.set_ylabel(self.labels[i])
+        return fig
 
 
 def treeprint(node):
@@ -291,6 +413,84 @@ def histogram(node, bins=10, range=None):
     if nb > HISTOGRAM_MAX_BINS:
         raise NotImplementedError(f"histogram takes at most {HISTOGRAM_MAX_BINS} bins on the device; got {nb}")
     return _per_component(_samples(node), lambda col: _histogram_vector(col, nb, range))
+
+
+# =============================================================================
+# joint histograms
+# =============================================================================
+def _joint_columns(what, nodes):
+    """corrcoef's rules: one float64 device vector per node, all of one length."""
+    cols = [_samples(node) for node in nodes]
+    for node, x in zip(nodes, cols):
+        if isinstance(x, _Scalar) or x.dim() != 1:
+            raise ValueError(f"{what} takes nodes that hold one sample vector each; {node} does not")
+    if any(x.shape[0] != cols[0].shape[0] for x in cols):
+        raise ValueError(f"{what}: the nodes hold different numbers of samples")
+    return cols
+
+
+def _limits_of(cols):
+    def limits(axis):
+        mom = _moment_rows(cols[axis])[0]
+        return mom["min"], mom["max"]
+
+    return limits
+
+
+def _device_edges(what, edges, pairs):
+    """The float64 edge arrays the kernel takes, within its caps."""
+    from . import native
+
+    out = [np.ascontiguousarray(e, dtype=np.float64) for e in edges]
+    for i, e in enumerate(out):
+        if len(e) < 2:
+            raise ValueError(f"{what}: `bins[{i}]` needs at least two edges")
+        if len(e) - 1 > native.HISTOGRAM2D_MAX_BINS:
+            raise NotImplementedError(f"{what} takes at most {native.HISTOGRAM2D_MAX_BINS} bins per axis on the "
+                                      f"device; got {len(e) - 1}")
+    for i, j in pairs:
+        cells = (len(out[i]) - 1) * (len(out[j]) - 1)
+        if cells > native.HISTOGRAM2D_MAX_CELLS:
+            raise NotImplementedError(f"{what} takes at most {native.HISTOGRAM2D_MAX_CELLS} cells per pair of nodes "
+                                      f"on the device; got {len(out[i]) - 1} x {len(out[j]) - 1} = {cells}")
+    return out
+
+
+def histogram2d(a, b, bins=10, range=None):
+    """np.histogram2d(a.samples_, b.samples_, bins=bins, range=range) -> (H, xedges, yedges) with H
+    as int64 (numpy's is float64 with the same values) and numpy's edges.  `bins`: an int,
+    (nx, ny), one edge array for both axes or (xedges | nx, yedges | ny), at most 1024 bins per axis
+    and 16384 cells; `range`: None or ((xlo, xhi) | None, (ylo, yhi) | None).  Without a range an
+    axis uses the minimum and maximum from the device (widened by 0.5 to each side when equal); a
+    non-finite one raises ValueError.  Both nodes must hold one sample vector of the same length.
+    One sweep over the two columns (pbh_histogram2d); only the counts come back."""
+    from . import native
+
+    cols = _joint_columns("histogram2d", (a, b))
+    edges = histogram2d_edges(bins, range, _limits_of(cols))
+    H = native.histogram2d(cols, _device_edges("histogram2d", edges, [(0, 1)]), [(0, 1)])[0]
+    return H, edges[0], edges[1]
+
+
+def pairgrid(*nodes, bins=30, range=None):
+    """The binned joint view of 2 to 16 sampled nodes, a PairGrid: every pair's 2-d histogram (all
+    K (K - 1) / 2 of them in one pbh_histogram2d launch) and every node's own histogram over the
+    same edges.  `bins`: one number of bins or one entry per node (at most 1024 per node, 16384
+    cells per pair); `range`: None or one (lo, hi) | None per node, the device minimum and maximum
+    otherwise.  Only the counts come back; PairGrid.draw() plots them."""
+    from . import native
+
+    K = len(nodes)
+    if K < 2 or K > native.HISTOGRAM2D_MAX_COLUMNS:
+        raise ValueError(f"pairgrid takes 2 to {native.HISTOGRAM2D_MAX_COLUMNS} nodes on the device; got {K}")
+    cols = _joint_columns("pairgrid", nodes)
+    edges = pairgrid_edges(K, bins, range, _limits_of(cols))
+    pairs = [(i, j) for i, j in np.ndindex(K, K) if i < j]
+    dev_edges = _device_edges("pairgrid", edges, pairs)
+    mats = native.histogram2d(cols, dev_edges, pairs)
+    # (uniform edges: np.linspace over the same ends gives pbh_histogram the same table)
+    diagonal = [native.histogram(x, len(e) - 1, (e[0], e[-1]))[0] for x, e in zip(cols, dev_edges)]
+    return PairGrid(cols[0].shape[0], [str(node) for node in nodes], edges, diagonal, dict(zip(pairs, mats)))
 
 
 # =============================================================================

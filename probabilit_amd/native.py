@@ -175,6 +175,8 @@ SUMMARY_TILE, SUMMARY_SPAN = 2048, 2048 * 1024
 SELECT_TILE, SELECT_SPAN = 16384, 16384 * 256
 SELECT_MAX_RANKS = 64
 HISTOGRAM_MAX_BINS = 4096
+HISTOGRAM2D_MAX_BINS, HISTOGRAM2D_MAX_CELLS = 1024, 16384  # per axis; bins_x * bins_y of one pair
+HISTOGRAM2D_MAX_COLUMNS, HISTOGRAM2D_MAX_PAIRS = 16, 120
 MOMENT_FIELDS = ("nan", "min", "max", "mean", "m2", "m3", "m4")
 
 
@@ -249,6 +251,58 @@ def histogram(x_dev, bins, range):
                                  ws.data_ptr(), nbytes, device.stream()), "pbh_histogram")
     host = device.to_host(counts)
     return (host[0] if x_dev.dim() == 1 else host), edges
+
+
+def histogram2d(cols, edges, pairs, ws_bytes=None):
+    """np.histogram2d(cols[i], cols[j], bins=(edges[i], edges[j]))[0] as an int64 host matrix per
+    (i, j) of `pairs`, in one launch (pbh_histogram2d).  cols: float64 device vectors of one length;
+    edges: one host edge array per column; an axis is uniform when its edges equal
+    np.linspace(e[0], e[-1], len(e)) bit for bit.  ws_bytes: the workspace to allocate and state
+    instead of pbh_histogram2d_workspace_size's (the library refuses one that is too small)."""
+    import ctypes
+
+    import torch
+
+    lib = _lib.load()
+    cols = list(cols)
+    for x in cols:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 1:
+            raise TypeError("float64 device vectors are required")
+        if x.shape[0] > 1 and x.stride(0) != 1:
+            raise ValueError("the samples of a column must be contiguous")
+    if len(edges) != len(cols):
+        raise ValueError("histogram2d: one edge array per column is required")
+    if cols and any(x.shape[0] != cols[0].shape[0] for x in cols):
+        raise ValueError("histogram2d: the columns hold different numbers of samples")
+    k, n = len(cols), (cols[0].shape[0] if cols else 0)
+    edges = [np.ascontiguousarray(e, dtype=np.float64).ravel() for e in edges]
+    if any(len(e) < 2 for e in edges):
+        raise ValueError("histogram2d: an axis needs at least two edges")
+    bins = np.array([len(e) - 1 for e in edges], dtype=np.int32)
+    with np.errstate(all="ignore"):  # (non-finite ends: the library refuses them)
+        uniform = np.array([np.linspace(e[0], e[-1], len(e)).tobytes() == e.tobytes() for e in edges], dtype=np.uint8)
+    flat = np.concatenate(edges) if edges else np.zeros(0)
+    ptrs = np.array([x.data_ptr() for x in cols], dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if ws_bytes is None:
+        b = ctypes.c_size_t()
+        _lib.check(lib.pbh_histogram2d_workspace_size(k, _lib.np_ptr(bins), ctypes.byref(b)),
+                   "pbh_histogram2d_workspace_size")
+        ws_bytes = b.value
+    ws = device.empty(max(int(ws_bytes), 8), "uint8")
+    inside = (pr >= 0).all(axis=1) & (pr < k).all(axis=1)  # (the library refuses the others)
+    shapes = [(int(bins[i]), int(bins[j])) if ok else (0, 0) for (i, j), ok in zip(pr.tolist(), inside.tolist())]
+    cells = sum(a * b for a, b in shapes)
+    counts = device.empty(max(cells, 1), "int64")
+    _lib.check(lib.pbh_histogram2d(_lib.np_ptr(ptrs), k, n, _lib.np_ptr(flat), _lib.np_ptr(bins), _lib.np_ptr(uniform),
+                                   _lib.np_ptr(pr), len(pr), counts.data_ptr(), ws.data_ptr(), int(ws_bytes),
+                                   device.stream()), "pbh_histogram2d")
+    host = device.to_host(counts)  # (the read-back: the host tables above have been consumed)
+    out, at = [], 0
+    for a, b in shapes:
+        out.append(host[at:at + a * b].reshape(a, b).copy())
+        at += a * b
+    return out
 
 
 def transpose(x_dev, rows, cols):
