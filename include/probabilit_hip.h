@@ -759,6 +759,57 @@ int pbh_histogram2d(const double* const* cols_host, int32_t k, int64_t n, const 
                     const int32_t* bins_host, const uint8_t* uniform_host, const int32_t* pairs_host, int32_t npairs,
                     int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* The conditional sums behind scipy.stats.binned_statistic(x_i, x_j, statistic, bins=edges_i) for
+ * count / sum / mean / std and behind the correlation ratio Var(E[x_j | x_i]) / Var(x_j), for
+ * npairs pairs (i, j) of k separate columns in one launch.  Columns, edges, bins and uniform flags
+ * are given as to pbh_histogram2d, except that a column which no pair bins by may carry
+ * bins_host[c] = 0 and then has no edges in edges_host at all.  pairs_host[2p], [2p + 1] = (i, j):
+ * column i is binned, column j gives the values; i == j is allowed.  centres_host[c] (k finite
+ * doubles) is the centre c_j subtracted from column c's values before they are summed; the mean
+ * of the column (pbh_moments) keeps s2 from cancelling for data such as 1e9 + noise.  For pair p
+ * and bin b of column i's edges, at offset o_p = sum of bins[i] over the earlier pairs (device;
+ * the call zeroes all three):
+ *     counts[o_p + b] = the number of rows whose x_i falls in bin b      (int64, np.histogram's)
+ *     s1[o_p + b]     = sum over those rows of fl(x_j - c_j)
+ *     s2[o_p + b]     = sum over those rows of fl(fl(x_j - c_j)^2)
+ * The bin rule is pbh_histogram2d's for one axis.  A row whose x_i is NaN, +-inf or outside
+ * [edges[0], edges[-1]] contributes to nothing.  The value is added as it is: a NaN or +-inf in x_j
+ * reaches s1 and s2 of its row's bin only, and never a count.
+ *
+ * One block per (row tile stride, pair): the edge table, bins[i] 32-bit counters and 2 bins[i]
+ * doubles in LDS (20 B per bin: at most 28 KiB), per counted row one LDS integer add and two LDS
+ * FP64 adds (one of each per wave when the wave's rows share a bin), per non-empty bin per block
+ * one global 64-bit integer add and two global FP64 adds.  16 B read per row per pair, no write
+ * proportional to n.
+ *
+ * Reproducibility: the counts are integer sums, identical on every run.  s1 and s2 are added by
+ * atomics in the order the waves and blocks arrive, so their last bits change from run to run;
+ * pbh_moments is the fixed-order summation, for a whole column.
+ *
+ * Error bound.  A floating-point sum of m terms t_k in any order (any tree) satisfies, to first
+ * order in the unit roundoff u = 2^-53,
+ *     |computed - sum t_k| <= (m - 1) u sum |t_k|,
+ * and the terms carry roundings of their own: d = fl(y - c) = (y - c)(1 + a), |a| <= u, and
+ * fl(d * d) = (y - c)^2 (1 + a)^2 (1 + b), |b| <= u.  With m = counts[b] and the sums over the
+ * bin's rows, to first order
+ *     |s1 - sum (y - c)|   <= m       u sum |y - c|          ((m - 1) + 1 rounding per term)
+ *     |s2 - sum (y - c)^2| <= (m + 2) u sum (y - c)^2        ((m - 1) + 3)
+ * (a term's subtraction enters its square twice).  Callers bound what they derive from s1 and s2
+ * from these two.
+ *
+ * n < 2^32.  ws >= pbh_binned_sums_workspace_size(k, bins) bytes, 8-byte aligned.  Every argument
+ * is checked before anything is enqueued; a bad call returns an error and launches nothing.  The
+ * call returns without synchronising: the host tables are uploaded by asynchronous copies on
+ * `stream` and must stay valid and unchanged until the stream has passed this call. */
+#define PBH_BINNED_MAX_BINS 1024    /* per binning column                                  */
+#define PBH_BINNED_MAX_COLUMNS 129  /* 128 inputs (MAX_VARIABLES) and one output           */
+#define PBH_BINNED_MAX_PAIRS 128
+int pbh_binned_sums_workspace_size(int32_t k, const int32_t* bins_host, size_t* bytes);
+int pbh_binned_sums(const double* const* cols_host, int32_t k, int64_t n, const double* edges_host,
+                    const int32_t* bins_host, const uint8_t* uniform_host, const double* centres_host,
+                    const int32_t* pairs_host, int32_t npairs, int64_t* counts, double* s1, double* s2, void* ws,
+                    size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,7 +65,8 @@ SYMBOLS = ["pbh_version", "pbh_last_error", "pbh_init", "pbh_fill_lhs", "pbh_fil
            "pbh_event_destroy", "pbh_event_record", "pbh_stream_wait_event", "pbh_event_synchronize",
            "pbh_set_serial", "pbh_ic_column_scores", "pbh_multivariate_normal", "pbh_dirichlet", "pbh_multinomial",
            "pbh_moments_workspace_size", "pbh_moments", "pbh_select_workspace_size", "pbh_select_ranks",
-           "pbh_histogram_workspace_size", "pbh_histogram", "pbh_histogram2d_workspace_size", "pbh_histogram2d"]
+           "pbh_histogram_workspace_size", "pbh_histogram", "pbh_histogram2d_workspace_size", "pbh_histogram2d",
+           "pbh_binned_sums_workspace_size", "pbh_binned_sums"]
 
 # kernel ids of pbh_kernel_name / pbh_timing_read (csrc/pbh_timing.h)
 KERNELS = ["k_lhs_ppf", "k_ppf", "k_scatter", "k_upsweep", "k_digit_hist", "k_rank_finish<scores>",
@@ -227,6 +228,8 @@ def load():
         "pbh_histogram": ([vp, i64, ctypes.c_int32, i64, vp, ctypes.c_int32, vp, vp, sz, vp], i32),
         "pbh_histogram2d_workspace_size": ([ctypes.c_int32, vp, ctypes.POINTER(sz)], i32),
         "pbh_histogram2d": ([vp, ctypes.c_int32, i64, vp, vp, vp, vp, ctypes.c_int32, vp, vp, sz, vp], i32),
+        "pbh_binned_sums_workspace_size": ([ctypes.c_int32, vp, ctypes.POINTER(sz)], i32),
+        "pbh_binned_sums": ([vp, ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, sz, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

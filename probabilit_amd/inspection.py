@@ -14,20 +14,28 @@ populates `node.samples_`.
     histogram2d(a, b, bins=10, range=None)        np.histogram2d(a.samples_, b.samples_, bins, range)
     pairgrid(*nodes, bins=30, range=None)         PairGrid: every pair's 2-d histogram, every node's own
     PairGrid.draw(fig=None)                       the K x K grid of those counts with matplotlib
+    binned_statistic(x, values, statistic="mean", bins=10, range=None)
+                                                  scipy.stats.binned_statistic(...)[:2]: count / sum / mean / std
+    sensitivity(output, *inputs, bins=32, binning="quantile")
+                                                  Sensitivity: E and std of the output per input bin, eta^2
+    Sensitivity.order() / .draw(fig=None)         the inputs by descending eta^2; the bars and curves
     treeprint(node)                               the graph above a node, one line per node
     plot(...)                                     probabilit_amd.plot (not provided)
 
 Limits: histograms take an integer number of at most 4096 uniform bins; joint histograms take
 numpy's forms of `bins` (edge arrays included) with at most 1024 bins per axis and 16384 cells per
-pair, a pair grid 2 to 16 nodes; quantile methods are linear, lower, higher, nearest and midpoint;
-samples row-sharded over a process group (`sample_device(group=...)` with more than one rank) are
+pair, a pair grid 2 to 16 nodes; binned statistics and sensitivity take at most 1024 bins per
+binning node and 128 value nodes or inputs, offer count, sum, mean and std, and add with atomics,
+so their floating-point results are not bit-reproducible from run to run; quantile methods are
+linear, lower, higher, nearest and midpoint; samples row-sharded over a process group (`sample_device(group=...)` with more than one rank) are
 not summarised across ranks.
 """
 
 import numpy as np
 
-# (histogram2d, pairgrid and PairGrid are public as well; the names a star import brings are the
-# reference module's and the first summaries, which tests/test_inspection_host.py pins)
+# (histogram2d, pairgrid, PairGrid, binned_statistic, sensitivity and Sensitivity are public as
+# well; the names a star import brings are the reference module's and the first summaries, which
+# tests/test_inspection_host.py pins)
 __all__ = ["summary", "quantile", "histogram", "corrcoef", "treeprint", "plot"]
 
 QUANTILE_METHODS = ("linear", "lower", "higher", "nearest", "midpoint")
@@ -128,6 +136,136 @@ def axis_edges(axis, bins, rng, limits):
             raise ValueError(f"`bins[{axis}]` must be monotonically increasing, when an array")
         return edges
     raise ValueError(f"`bins[{axis}]` must be a scalar or 1d array")
+
+
+def uniform_edges(bins, lo, hi):
+    """The `bins` + 1 uniform edges over a column's minimum and maximum, numpy's way (axis_edges
+    without a range: widened by 0.5 to each side when equal, ValueError when not finite)."""
+    return axis_edges(0, bins, None, lambda axis: (lo, hi))
+
+
+def quantile_ranks(n, bins):
+    """The `bins` + 1 zero-based ranks of the equal-probability edges of n samples: the order
+    statistics np.quantile(x, k / bins, method="nearest") takes, k = 0 .. bins, so rank 0 (the
+    minimum) first and rank n - 1 (the maximum) last."""
+    import operator
+
+    nb = operator.index(bins)
+    if nb < 1:
+        raise ValueError("`bins` must be positive")
+    return quantile_indexes(n, np.arange(nb + 1) / nb, "nearest")[0].astype(np.int64)
+
+
+def quantile_edges(values_at_ranks):
+    """The edge table from the order statistics at quantile_ranks: the values as they are, ties
+    kept as repeated edges (which give empty bins); a constant column's range is widened by 0.5 to
+    each side as axis_edges does.  A non-finite value (a NaN among the samples sorts last) raises
+    ValueError."""
+    e = np.array(values_at_ranks, dtype=np.float64).ravel()
+    if len(e) < 2:
+        raise ValueError("quantile_edges needs at least two order statistics")
+    if not np.all(np.isfinite(e)):
+        raise ValueError(f"autodetected range of [{e[0]}, {e[-1]}] is not finite")
+    if np.any(e[:-1] > e[1:]):
+        raise ValueError("the order statistics must be non-decreasing")
+    if e[0] == e[-1]:
+        e[0], e[-1] = e[0] - 0.5, e[-1] + 0.5
+    return e
+
+
+BINNED_STATISTICS = ("count", "sum", "mean", "std")
+
+
+def binned_finish(count, s1, s2, centre, statistic):
+    """scipy.stats.binned_statistic's `statistic` per bin, as float64, from pbh_binned_sums' raw
+    sums about `centre` (count rows, s1 = sum(y - centre), s2 = sum((y - centre)^2)):
+    count; sum = s1 + count centre; mean = centre + s1 / count; std (ddof 0) =
+    sqrt(max(s2 / count - (s1 / count)^2, 0)).  Empty bins give NaN for mean and std and 0 for
+    count and sum, as scipy does."""
+    if statistic not in BINNED_STATISTICS:
+        raise ValueError(f"statistic {statistic!r} is not one of {BINNED_STATISTICS}")
+    cnt = np.asarray(count, dtype=np.float64)
+    s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+    if not (cnt.shape == s1.shape == s2.shape):
+        raise ValueError("count, s1 and s2 must have one shape")
+    centre = float(centre)
+    if statistic == "count":
+        return cnt.copy()
+    if statistic == "sum":
+        return np.where(cnt > 0, s1 + cnt * centre, 0.0)
+    with np.errstate(all="ignore"):
+        m1 = s1 / cnt
+        if statistic == "mean":
+            return np.where(cnt > 0, centre + m1, np.nan)
+        var = s2 / cnt - m1 * m1
+        return np.where(cnt > 0, np.sqrt(np.where(var < 0.0, 0.0, var)), np.nan)  # (a NaN variance stays NaN)
+
+
+def correlation_ratio(count, s1, s2):
+    """eta^2 = Var(E[Y | X]) / Var(Y) over the bins of X, from the raw sums about any centre:
+    sum_b n_b (s1_b / n_b - S1 / N)^2 / (S2 - S1^2 / N) with S1, S2, N the totals over the bins, so
+    the base is the rows inside the edges.  NaN when the denominator is not positive (no rows, a
+    constant Y, or a non-finite sum)."""
+    cnt = np.asarray(count, dtype=np.float64)
+    s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+    if not (cnt.shape == s1.shape == s2.shape) or cnt.ndim != 1:
+        raise ValueError("count, s1 and s2 must be vectors of one length")
+    N = cnt.sum()
+    if not N > 0:
+        return float("nan")
+    has = cnt > 0
+    S1, S2 = s1[has].sum(), s2[has].sum()
+    with np.errstate(all="ignore"):
+        den = S2 - S1 * S1 / N
+        if not den > 0.0:
+            return float("nan")
+        dev = s1[has] / cnt[has] - S1 / N
+        return float((cnt[has] * dev * dev).sum() / den)
+
+
+class Sensitivity:
+    """What K inputs explain of one output (sensitivity): `output` and `labels` (str(node)),
+    `count` samples, and per input k `edges[k]`, `counts[k]` (int64 rows per bin),
+    `conditional_mean[k]` and `conditional_std[k]` (E and std of the output given the input's bin;
+    NaN for an empty bin), and `first_order`, the (K,) correlation ratios eta^2."""
+
+    def __init__(self, output, labels, count, edges, counts, conditional_mean, conditional_std, first_order):
+        self.output, self.labels, self.count = str(output), list(labels), int(count)
+        self.edges, self.counts = list(edges), list(counts)
+        self.conditional_mean, self.conditional_std = list(conditional_mean), list(conditional_std)
+        self.first_order = np.asarray(first_order, dtype=np.float64)
+
+    def order(self):
+        """The inputs' indices by descending eta^2 (NaN last, ties in the given order)."""
+        key = np.where(np.isnan(self.first_order), -np.inf, self.first_order)
+        return np.argsort(-key, kind="stable")
+
+    def draw(self, fig=None):
+        """Draw with matplotlib and return the figure: on top the horizontal bars of eta^2 in
+        descending order, below it every input's conditional-mean curve over its bin centres, in
+        the same order.  Draws what the object holds: nothing is downloaded."""
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("Sensitivity.draw needs matplotlib, which is not installed") from e
+        order = self.order()
+        k = len(order)
+        if fig is None:
+            fig = plt.figure(figsize=(6.0, 2.0 + 0.25 * k + 1.8 * k))
+        axes = fig.subplots(k + 1, 1, squeeze=False)[:, 0]
+        top = axes[0]
+        top.barh(np.arange(k), self.first_order[order])
+        top.set_yticks(np.arange(k))
+        top.set_yticklabels([self.labels[i] for i in order])
+        top.invert_yaxis()
+        top.set_xlabel(f"first-order share of Var({self.output})")
+        for ax, i in zip(axes[1:], order):
+            e = np.asarray(self.edges[i], dtype=np.float64)
+            has = np.asarray(self.counts[i]) > 0
+            ax.plot((0.5 * (e[:-1] + e[1:]))[has], np.asarray(self.conditional_mean[i])[has], marker=".")
+            ax.set_xlabel(self.labels[i])
+            ax.set_ylabel(f"E[{self.output} | bin]")
+        return fig
 
 
 def histogram2d_edges(bins, rng, limits):
@@ -491,6 +629,101 @@ def pairgrid(*nodes, bins=30, range=None):
     # (uniform edges: np.linspace over the same ends gives pbh_histogram the same table)
     diagonal = [native.histogram(x, len(e) - 1, (e[0], e[-1]))[0] for x, e in zip(cols, dev_edges)]
     return PairGrid(cols[0].shape[0], [str(node) for node in nodes], edges, diagonal, dict(zip(pairs, mats)))
+
+
+# =============================================================================
+# conditional statistics, first-order sensitivity
+# =============================================================================
+def _binning_edges(what, e):
+    """One float64 edge array the kernel takes, within its cap."""
+    from . import native
+
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    if len(e) < 2:
+        raise ValueError(f"{what}: `bins` needs at least two edges")
+    if len(e) - 1 > native.BINNED_MAX_BINS:
+        raise NotImplementedError(f"{what} takes at most {native.BINNED_MAX_BINS} bins on the device; got {len(e) - 1}")
+    return e
+
+
+def _centre(col):
+    """The column's mean from the device, or 0 where it is not finite (the sums then carry the
+    NaN or inf themselves)."""
+    mean = _moment_rows(col)[0]["mean"]
+    return mean if np.isfinite(mean) else 0.0
+
+
+def binned_statistic(x, values, statistic="mean", bins=10, range=None):
+    """scipy.stats.binned_statistic(x.samples_, values.samples_, statistic, bins, range) without
+    its N-sized binnumber: (statistic, bin_edges), the statistic as float64.  `statistic`: count,
+    sum, mean or std (median, min, max and callables have no device path); `values`: one node, or a
+    list of up to 128, which gives a (len, bins) result; `bins`: a number of bins or an array of
+    edges, at most 1024 bins; `range`: (lo, hi) or None, then the minimum and maximum of x from the
+    device (widened by 0.5 to each side when equal; a non-finite one raises ValueError).  The bin
+    rule is numpy's: the last bin is closed and rows outside the edges or with a NaN x are dropped.
+    Every node must hold one sample vector of the same length.  One sweep over the columns
+    (pbh_binned_sums) about each value column's mean; its sums come from atomics, so the last bits
+    of sum, mean and std change from run to run.  Only the per-bin numbers come back."""
+    from . import native
+
+    if statistic not in BINNED_STATISTICS:
+        raise ValueError(f"statistic {statistic!r} is not one of {BINNED_STATISTICS}; median, min, max and callables "
+                         "are not provided on the device")
+    many = isinstance(values, (list, tuple))
+    vals = list(values) if many else [values]
+    if not 1 <= len(vals) <= native.BINNED_MAX_PAIRS:
+        raise ValueError(f"binned_statistic takes 1 to {native.BINNED_MAX_PAIRS} value nodes; got {len(vals)}")
+    cols = _joint_columns("binned_statistic", (x, *vals))
+    edges = axis_edges(0, bins, range, _limits_of(cols))
+    dev_edges = _binning_edges("binned_statistic", edges)
+    centres = [0.0] + [0.0 if statistic == "count" else _centre(c) for c in cols[1:]]
+    raw = native.binned_sums(cols, [dev_edges] + [None] * len(vals), [(0, 1 + v) for v in np.arange(len(vals))], centres)
+    out = np.stack([binned_finish(c, s1, s2, ctr, statistic) for (c, s1, s2), ctr in zip(raw, centres[1:])])
+    return (out if many else out[0]), edges
+
+
+def sensitivity(output, *inputs, bins=32, binning="quantile"):
+    """Which of 1 to 128 inputs drive `output`: a Sensitivity with, per input, the output's mean
+    and std given the input's bin and the correlation ratio eta^2 = Var(E[output | input]) /
+    Var(output), the given-data estimate of the first-order share of the variance, which unlike
+    corrcoef also sees non-monotone dependence (products, maxima, comparisons).  `bins`: 1 to 1024
+    per input; binning="quantile": equal-probability edges per input, the order statistics at ranks
+    round(k (n - 1) / bins) (pbh_select_ranks; ties give repeated edges and empty bins),
+    binning="uniform": uniform edges from the input's minimum to its maximum; a constant input's
+    range is widened by 0.5 to each side.  One pbh_binned_sums launch covers all inputs; its sums
+    come from atomics, so the last bits change from run to run.  Nothing N-sized comes back."""
+    import operator
+
+    from . import native
+
+    K = len(inputs)
+    if not 1 <= K <= native.BINNED_MAX_PAIRS:
+        raise ValueError(f"sensitivity takes 1 to {native.BINNED_MAX_PAIRS} inputs on the device; got {K}")
+    if binning not in ("quantile", "uniform"):
+        raise ValueError(f"binning {binning!r} is not 'quantile' or 'uniform'")
+    try:
+        nb = operator.index(bins)
+    except TypeError as e:
+        raise TypeError("`bins` must be an integer") from e
+    if not 1 <= nb <= native.BINNED_MAX_BINS:
+        raise ValueError(f"sensitivity takes 1 to {native.BINNED_MAX_BINS} bins per input; got {nb}")
+    cols = _joint_columns("sensitivity", (output, *inputs))
+    n = cols[0].shape[0]
+    edges = []
+    for x in cols[1:]:
+        if binning == "quantile":
+            ranks = quantile_ranks(n, nb)
+            got, _ = _select(x, ranks)
+            edges.append(quantile_edges([got[r] for r in ranks.tolist()]))
+        else:
+            mom = _moment_rows(x)[0]
+            edges.append(uniform_edges(nb, mom["min"], mom["max"]))
+    centre = _centre(cols[0])
+    raw = native.binned_sums(cols, [None] + edges, [(1 + k, 0) for k in np.arange(K)], [centre] + [0.0] * K)
+    return Sensitivity(output, [str(node) for node in inputs], n, edges, [c for c, _, _ in raw],
+                       [binned_finish(c, s1, s2, centre, "mean") for c, s1, s2 in raw],
+                       [binned_finish(c, s1, s2, centre, "std") for c, s1, s2 in raw],
+                       [correlation_ratio(c, s1, s2) for c, s1, s2 in raw])
 
 
 # =============================================================================

@@ -177,6 +177,7 @@ SELECT_MAX_RANKS = 64
 HISTOGRAM_MAX_BINS = 4096
 HISTOGRAM2D_MAX_BINS, HISTOGRAM2D_MAX_CELLS = 1024, 16384  # per axis; bins_x * bins_y of one pair
 HISTOGRAM2D_MAX_COLUMNS, HISTOGRAM2D_MAX_PAIRS = 16, 120
+BINNED_MAX_BINS, BINNED_MAX_COLUMNS, BINNED_MAX_PAIRS = 1024, 129, 128  # 128 inputs and one output
 MOMENT_FIELDS = ("nan", "min", "max", "mean", "m2", "m3", "m4")
 
 
@@ -302,6 +303,65 @@ def histogram2d(cols, edges, pairs, ws_bytes=None):
     for a, b in shapes:
         out.append(host[at:at + a * b].reshape(a, b).copy())
         at += a * b
+    return out
+
+
+def binned_sums(cols, edges, pairs, centres, ws_bytes=None):
+    """[(count int64[b], s1 float64[b], s2 float64[b])] per (i, j) of `pairs`, in one launch
+    (pbh_binned_sums): over the b bins of edges[i], the rows of cols[i] in the bin (np.histogram's
+    counts) and the sums of cols[j] - centres[j] and of its square over those rows.  cols: float64
+    device vectors of one length; edges: one host edge array per column, None (or an empty one) for
+    a column that only gives values; an axis is uniform when its edges equal
+    np.linspace(e[0], e[-1], len(e)) bit for bit; centres: one float per column.  The sums come
+    from atomics and change in their last bits from run to run.  ws_bytes: the workspace to
+    allocate and state instead of pbh_binned_sums_workspace_size's."""
+    import ctypes
+
+    import torch
+
+    lib = _lib.load()
+    cols = list(cols)
+    for x in cols:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 1:
+            raise TypeError("float64 device vectors are required")
+        if x.shape[0] > 1 and x.stride(0) != 1:
+            raise ValueError("the samples of a column must be contiguous")
+    if len(edges) != len(cols):
+        raise ValueError("binned_sums: one edge array (or None) per column is required")
+    centres = np.ascontiguousarray(centres, dtype=np.float64).ravel()
+    if len(centres) != len(cols):
+        raise ValueError("binned_sums: one centre per column is required")
+    if cols and any(x.shape[0] != cols[0].shape[0] for x in cols):
+        raise ValueError("binned_sums: the columns hold different numbers of samples")
+    k, n = len(cols), (cols[0].shape[0] if cols else 0)
+    edges = [np.zeros(0) if e is None else np.ascontiguousarray(e, dtype=np.float64).ravel() for e in edges]
+    if any(len(e) == 1 for e in edges):
+        raise ValueError("binned_sums: a binning column needs at least two edges")
+    bins = np.array([max(len(e) - 1, 0) for e in edges], dtype=np.int32)
+    with np.errstate(all="ignore"):  # (non-finite ends: the library refuses them)
+        uniform = np.array([len(e) > 0 and np.linspace(e[0], e[-1], len(e)).tobytes() == e.tobytes() for e in edges],
+                           dtype=np.uint8)
+    flat = np.concatenate(edges + [np.zeros(1)])  # (never empty: its pointer is not NULL)
+    ptrs = np.array([x.data_ptr() for x in cols], dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if ws_bytes is None:
+        b = ctypes.c_size_t()
+        _lib.check(lib.pbh_binned_sums_workspace_size(k, _lib.np_ptr(bins), ctypes.byref(b)),
+                   "pbh_binned_sums_workspace_size")
+        ws_bytes = b.value
+    ws = device.empty(max(int(ws_bytes), 8), "uint8")
+    inside = (pr >= 0).all(axis=1) & (pr < k).all(axis=1)  # (the library refuses the others)
+    sizes = [int(bins[i]) if ok else 0 for (i, _), ok in zip(pr.tolist(), inside.tolist())]
+    total = max(sum(sizes), 1)
+    counts, s1, s2 = device.empty(total, "int64"), device.empty(total), device.empty(total)
+    _lib.check(lib.pbh_binned_sums(_lib.np_ptr(ptrs), k, n, _lib.np_ptr(flat), _lib.np_ptr(bins), _lib.np_ptr(uniform),
+                                   _lib.np_ptr(centres), _lib.np_ptr(pr), len(pr), counts.data_ptr(), s1.data_ptr(),
+                                   s2.data_ptr(), ws.data_ptr(), int(ws_bytes), device.stream()), "pbh_binned_sums")
+    hc, h1, h2 = (device.to_host(t) for t in (counts, s1, s2))  # (the read-back: the host tables are consumed)
+    out, at = [], 0
+    for b in sizes:
+        out.append((hc[at:at + b].copy(), h1[at:at + b].copy(), h2[at:at + b].copy()))
+        at += b
     return out
 
 
