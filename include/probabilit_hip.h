@@ -181,7 +181,10 @@ int pbh_fill_uniform(uint64_t seed, int64_t row0, int64_t nrows, int col0, int n
  * modeling.py:484-486, rows [row0, row0 + nrows) of it.  key_host / pos: the generator's state
  * (RandomState.get_state()[1:3]).  Workspace: pbh_mt19937_workspace_size (8 B per draw + the
  * 107 KB jump table).  pbh_mt19937_advance returns numpy's state after nwords 32-bit draws (key
- * block + pos), so that a caller-owned or the global RandomState advances exactly as in numpy. */
+ * block + pos), so that a caller-owned or the global RandomState advances exactly as in numpy.
+ * The jump table reaches words below 2^44 of the key block's sequence (word 0 = key[0]): a call whose
+ * last word, pos + 2 (row0 + nrows) d - 1 or pos + nwords - 1, lies at or beyond 2^44 is
+ * PBH_ERR_INVALID and writes nothing. */
 int pbh_mt19937_workspace_size(int64_t nrows, int32_t d, size_t* bytes);
 int pbh_mt19937_random(const uint32_t* key_host, int32_t pos, int64_t row0, int64_t nrows, int32_t d, double* q,
                        int64_t ldq, void* ws, size_t ws_bytes, void* stream);

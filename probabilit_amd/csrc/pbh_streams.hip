@@ -223,6 +223,13 @@ int64_t mt_segment(int64_t total) {
   return seg;
 }
 
+// The jump table holds x^(2^i) for i < kJumpBits, so a word at or beyond 2^kJumpBits of the
+// key block's sequence cannot be reached (window_before would drop the high bits of the distance).
+constexpr int64_t kMtWordLimit = (int64_t)1 << mt::kJumpBits;
+
+// first + count - 1 < kMtWordLimit for count >= 1, without overflow
+bool mt_in_range(int64_t first, int64_t count) { return first < kMtWordLimit && count <= kMtWordLimit - first; }
+
 }  // namespace
 }  // namespace pbh
 
@@ -268,6 +275,14 @@ extern "C" int pbh_mt19937_random(const uint32_t* key_host, int32_t pos, int64_t
   PBH_REQUIRE(key_host && ws && row0 >= 0 && nrows >= 0 && d >= 0 && pos >= 0 && pos <= mt::kN,
               "pbh_mt19937_random: bad arguments");
   PBH_REQUIRE(nrows * (int64_t)d == 0 || (q && ldq >= nrows), "pbh_mt19937_random: bad output");
+  if (nrows > 0 && d > 0) {  // every factor is checked before it is multiplied
+    const int64_t per_row = 2 * (int64_t)d;
+    PBH_REQUIRE(row0 <= kMtWordLimit / per_row && nrows <= kMtWordLimit / per_row &&
+                    mt_in_range((int64_t)pos + row0 * per_row, nrows * per_row),
+                "pbh_mt19937_random: the draws end beyond word 2^%d of the stream, the reach of the jump table "
+                "(pos %d, row0 %lld, nrows %lld, d %d)",
+                mt::kJumpBits, (int)pos, (long long)row0, (long long)nrows, (int)d);
+  }
   size_t need = 0;
   pbh_mt19937_workspace_size(nrows, d, &need);
   hipStream_t s = as_stream(stream);
@@ -295,6 +310,10 @@ extern "C" int pbh_mt19937_advance(const uint32_t* key_host, int32_t pos, int64_
                                    int32_t* pos_out, void* ws, size_t ws_bytes, void* stream) {
   PBH_REQUIRE(key_host && key_out_host && pos_out && ws && nwords >= 0 && pos >= 0 && pos <= mt::kN,
               "pbh_mt19937_advance: bad arguments");
+  PBH_REQUIRE(nwords == 0 || mt_in_range(pos, nwords),
+              "pbh_mt19937_advance: the draws end beyond word 2^%d of the stream, the reach of the jump table "
+              "(pos %d, nwords %lld)",
+              mt::kJumpBits, (int)pos, (long long)nwords);
   size_t need = 0;
   pbh_mt19937_workspace_size(0, 0, &need);
   hipStream_t s = as_stream(stream);

@@ -1,5 +1,6 @@
 """Views inside sentinel-filled device buffers for tests that call one C-ABI entry point directly
-(test_gpu_ppf_kernels.py, test_gpu_table_kernel.py, the generator test of test_gpu_qmc.py).
+(test_gpu_ppf_kernels.py, test_gpu_table_kernel.py, the generator test of test_gpu_qmc.py,
+test_gpu_stream_kernels.py, test_gpu_mvar_kernels.py).
 
 Every input and output of such a call is a strided view at an element offset inside a wider
 buffer whose other elements hold one fixed NaN bit pattern; the buffers are compared as int64, so
@@ -67,6 +68,57 @@ class View:
     def untouched(self):
         """The whole buffer, the view included, still holds the sentinel."""
         return bool((self.buf == SENT).all())
+
+
+class Block(View):
+    """A column-major output block of ncols columns x nrows rows with a leading dimension of
+    nrows + 3, at element offset `off` inside a sentinel buffer, followed by `after` more sentinels
+    inside the view (one whole column unless given): what a generator or sampler entry point writes
+    through (q, ldq).  Everything is compared on the device, so a block of 10^8 elements costs no
+    host copy."""
+
+    def __init__(self, nrows, ncols, off=5, after=None):
+        self.nrows, self.ncols, self.ld = int(nrows), int(ncols), int(nrows) + 3
+        self.after = self.ld if after is None else int(after)
+        super().__init__(self.ncols * self.ld + self.after, off=off)
+
+    def cols(self):
+        """The block itself, (ncols, nrows): an int64 device tensor over the buffer."""
+        return self.dev()[:self.ncols * self.ld].reshape(self.ncols, self.ld)[:, :self.nrows]
+
+    def rows(self, dtype=np.float64):
+        """The block on the host, (nrows, ncols)."""
+        return self.cols().cpu().numpy().view(dtype).T
+
+    def assert_clean(self):
+        """The three gap rows of every column, the column after the last and everything around the
+        block still hold the sentinel."""
+        v = self.dev()
+        body = v[:self.ncols * self.ld].reshape(self.ncols, self.ld)
+        assert bool((body[:, self.nrows:] == SENT).all()), "a gap row was written"
+        assert bool((v[self.ncols * self.ld:] == SENT).all()), "the column after the last was written"
+        assert self.intact(), "a write outside the block"
+
+    def assert_bits(self, ref, what=""):
+        """assert_clean, and the block equals the (nrows, ncols) host array `ref` (float64 or int64)
+        bit for bit."""
+        torch = _torch()
+        self.assert_clean()
+        ref = np.asarray(ref)
+        assert ref.shape == (self.nrows, self.ncols), (ref.shape, self.nrows, self.ncols)
+        want = torch.from_numpy(np.ascontiguousarray(bits(ref).T)).to(self.buf.device)
+        self.assert_same(want, what)
+
+    def assert_same(self, want, what=""):
+        """The block equals the (ncols, nrows) int64 device tensor `want`."""
+        torch = _torch()
+        got = self.cols()
+        assert tuple(want.shape) == tuple(got.shape), (tuple(want.shape), tuple(got.shape))
+        ne = got != want
+        if bool(ne.any()):
+            c, r = (int(x) for x in torch.nonzero(ne)[0])
+            raise AssertionError(f"{what}: {int(ne.sum())} of {ne.numel()} elements differ, first at row {r} column {c}: "
+                                 f"got {int(got[c, r]):#018x}, want {int(want[c, r]):#018x}")
 
 
 class Flag:
