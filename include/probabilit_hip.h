@@ -230,6 +230,13 @@ int pbh_lhs_reference_perms(const uint64_t* state_host, const uint64_t* inc_host
  * retry doubles it); sigmas = 0 only reads it.  pbh_lhs_reference_stats: the last call's record
  * (device = 1: decoded on the device; attempts; ambiguous draws walked on the host). */
 int pbh_lhs_reference_band(double sigmas, double* previous);
+/* The band table the decode would classify n rows against at a half-width of `sigmas`, for tests
+ * (host only: no HIP call).  *tcap: the draws classified per column; *nband: the table's entries,
+ * one per 1024 draws; out_host (may be NULL when out_entries = 0) receives the first
+ * min(*nband, out_entries) pairs (expected steps done, half-width in steps).  2 <= n < 2^31,
+ * sigmas > 0. */
+int pbh_lhs_reference_band_table(int64_t n, double sigmas, double* out_host, int64_t out_entries, int64_t* nband,
+                                 int64_t* tcap);
 /* The process cache of inverse-CDF setup tables (gamma / beta guides, poisson / binom / nbinom CDF
  * tables, keyed by their scalar parameters; pbh_table_cache.hip): tables held, their bytes, and
  * the calls served from it.  The cache holds at most 1 GiB and 4 096 tables of <= 64 MiB each

@@ -284,9 +284,10 @@ __global__ __launch_bounds__(kT) void k_dec_compact(DecParams pr, const double2*
   }
 }
 
-// per-draw accept flags: the decided ones and the walk's
+// per-draw accept flags: the decided ones and the walk's (an ambiguous draw past the walk's cap
+// counts as rejected: k_dec_finish finds it wrong if the column had not ended before it)
 __device__ __forceinline__ uint32_t accept_flags(const uint8_t* c, const uint32_t* pre, const uint8_t* dec,
-                                                 int64_t nb, uint32_t* sh) {
+                                                 int64_t nb, uint32_t cap, uint32_t* sh) {
   uint32_t namb = 0;
 #pragma unroll
   for (int j = 0; j < kPer; ++j) namb += c[j] == kAmb;
@@ -296,7 +297,10 @@ __device__ __forceinline__ uint32_t accept_flags(const uint8_t* c, const uint32_
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     uint32_t a = c[j] == kAcc;
-    if (c[j] == kAmb) a = dec[amb++];
+    if (c[j] == kAmb) {
+      a = amb < cap ? dec[amb] : 0u;
+      ++amb;
+    }
     bits |= a << j;
   }
   return bits;
@@ -304,12 +308,12 @@ __device__ __forceinline__ uint32_t accept_flags(const uint8_t* c, const uint32_
 
 __global__ __launch_bounds__(kT) void k_dec_accsum(DecParams pr, const uint8_t* __restrict__ cls,
                                                    const uint32_t* __restrict__ pre, const uint8_t* __restrict__ dec,
-                                                   uint32_t* __restrict__ tot2) {
+                                                   uint32_t cap, uint32_t* __restrict__ tot2) {
   __shared__ uint32_t sh[kT / 64];
   const int64_t tau0 = (int64_t)blockIdx.x * kBlk + (int64_t)threadIdx.x * kPer;
   uint8_t c[kPer];
   load_cls(cls, tau0, c);
-  const uint32_t bits = accept_flags(c, pre, dec, pr.nb, sh);
+  const uint32_t bits = accept_flags(c, pre, dec, pr.nb, cap, sh);
   uint32_t total;
   (void)scan256(__popc(bits), sh, &total);
   if (threadIdx.x == 0) tot2[blockIdx.x] = total;
@@ -318,15 +322,15 @@ __global__ __launch_bounds__(kT) void k_dec_accsum(DecParams pr, const uint8_t* 
 // every decision against the rule at the state its prefix implies; the swap targets; the end
 __global__ __launch_bounds__(kT) void k_dec_finish(DecParams pr, const uint32_t* __restrict__ W,
                                                    const uint8_t* __restrict__ cls, const uint32_t* __restrict__ pre,
-                                                   const uint8_t* __restrict__ dec, const uint32_t* __restrict__ pre2,
-                                                   int64_t* __restrict__ P, int c, int32_t* __restrict__ J,
-                                                   int32_t* __restrict__ err) {
+                                                   const uint8_t* __restrict__ dec, uint32_t cap,
+                                                   const uint32_t* __restrict__ pre2, int64_t* __restrict__ P, int c,
+                                                   int32_t* __restrict__ J, int32_t* __restrict__ err) {
   __shared__ uint32_t sh[kT / 64];
   const int64_t tau0 = (int64_t)blockIdx.x * kBlk + (int64_t)threadIdx.x * kPer;
   const int64_t N1 = pr.n - 1;
   uint8_t cl[kPer];
   load_cls(cls, tau0, cl);
-  const uint32_t bits = accept_flags(cl, pre, dec, pr.nb, sh);
+  const uint32_t bits = accept_flags(cl, pre, dec, pr.nb, cap, sh);
   uint32_t total;
   int64_t S = (int64_t)pre2[blockIdx.x] + scan256(__popc(bits), sh, &total);
   if (S >= N1) return;
@@ -655,8 +659,11 @@ int decode_attempt(const DecParams& base, const uint64_t* state_host, const uint
     PBH_CHECK_HIP(hipMemcpyAsync(pn.list, pre + 2 * pr.nb + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     PBH_CHECK_HIP(hipStreamSynchronize(s));
     memcpy(&namb, pn.list, sizeof(uint32_t));
-    if ((int64_t)namb > cap) return PBH_OK;  // too many to walk: the host shuffles
     namb_total += namb;
+    // The walk takes the column's first `cap` ambiguous draws.  A column that ends inside them is
+    // decoded (what lies past its end is never read); one that does not fails k_dec_finish's
+    // check or never finds its end, and the attempt with it.
+    if ((int64_t)namb > cap) namb = (uint32_t)cap;
     if (namb) {
       PBH_CHECK_HIP(hipMemcpyAsync(pn.list, list, (size_t)namb * sizeof(uint2), hipMemcpyDeviceToHost, s));
       PBH_CHECK_HIP(hipStreamSynchronize(s));
@@ -679,11 +686,12 @@ int decode_attempt(const DecParams& base, const uint64_t* state_host, const uint
       }
       PBH_CHECK_HIP(hipMemcpyAsync(dec, pn.dec, namb, hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(k_dec_accsum, dim3(nb), dim3(kT), 0, s, pr, cls, pre, dec, tot2);
+    hipLaunchKernelGGL(k_dec_accsum, dim3(nb), dim3(kT), 0, s, pr, cls, pre, dec, (uint32_t)cap, tot2);
     PBH_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, s, tot2, pr.nb, pr.nb, pre2, pr.nb + 1);
     PBH_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_dec_finish, dim3(nb), dim3(kT), 0, s, pr, W, cls, pre, dec, pre2, P, c, Jc, err);
+    hipLaunchKernelGGL(k_dec_finish, dim3(nb), dim3(kT), 0, s, pr, W, cls, pre, dec, (uint32_t)cap, pre2, P, c, Jc,
+                       err);
     PBH_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_dec_seal, dim3(1), dim3(64), 0, s, err, P, c, okc);
     PBH_CHECK_LAUNCH();
@@ -775,6 +783,19 @@ extern "C" int pbh_lhs_reference_band(double sigmas, double* previous) {
   PBH_REQUIRE(sigmas >= 0.0 && sigmas < 1e6, "pbh_lhs_reference_band: bad width");
   if (previous) *previous = pbh::g_band_sigmas;
   if (sigmas > 0.0) pbh::g_band_sigmas = sigmas;
+  return PBH_OK;
+}
+
+extern "C" int pbh_lhs_reference_band_table(int64_t n, double sigmas, double* out_host, int64_t out_entries,
+                                            int64_t* nband, int64_t* tcap) {
+  PBH_REQUIRE(n >= 2 && n < ((int64_t)1 << 31) && sigmas > 0.0 && nband && tcap && out_entries >= 0 &&
+                  (out_host || out_entries == 0),
+              "pbh_lhs_reference_band_table: bad arguments");
+  std::vector<double> band;
+  *tcap = pbh::band_table(n, sigmas, band);
+  *nband = (int64_t)band.size() / 2;
+  const int64_t m = std::min<int64_t>(*nband, out_entries);
+  if (m > 0) memcpy(out_host, band.data(), (size_t)m * 2 * sizeof(double));
   return PBH_OK;
 }
 

@@ -1,6 +1,6 @@
 """Views inside sentinel-filled device buffers for tests that call one C-ABI entry point directly
 (test_gpu_ppf_kernels.py, test_gpu_table_kernel.py, the generator test of test_gpu_qmc.py,
-test_gpu_stream_kernels.py, test_gpu_mvar_kernels.py).
+test_gpu_stream_kernels.py, test_gpu_mvar_kernels.py, test_gpu_lhs_decode_kernels.py).
 
 Every input and output of such a call is a strided view at an element offset inside a wider
 buffer whose other elements hold one fixed NaN bit pattern; the buffers are compared as int64, so
@@ -119,6 +119,62 @@ class Block(View):
             c, r = (int(x) for x in torch.nonzero(ne)[0])
             raise AssertionError(f"{what}: {int(ne.sum())} of {ne.numel()} elements differ, first at row {r} column {c}: "
                                  f"got {int(got[c, r]):#018x}, want {int(want[c, r]):#018x}")
+
+
+SENT32 = -0x5EED_0BAD  # no stratum, rank or count is negative
+
+
+class Block32:
+    """Block's int32 sibling: a column-major block of ncols columns x nrows rows of int32 with a
+    leading dimension of nrows + 3, at element offset `off` inside a buffer of SENT32, followed by
+    `after` more sentinels (one whole column unless given): what an entry point writes through
+    (strata, lds)."""
+
+    def __init__(self, nrows, ncols, off=5, after=None):
+        from probabilit_amd import device
+
+        torch = _torch()
+        self.nrows, self.ncols, self.ld = int(nrows), int(ncols), int(nrows) + 3
+        self.after = self.ld if after is None else int(after)
+        self.n = self.ncols * self.ld + self.after
+        self.lo = PAD + off
+        self.buf = torch.full((self.lo + self.n + PAD,), SENT32, dtype=torch.int32, device=device.device())
+        self.ptr = ctypes.c_void_p(self.buf.data_ptr() + 4 * self.lo)
+
+    def dev(self):
+        return self.buf[self.lo:self.lo + self.n]
+
+    def cols(self):
+        """The block itself, (ncols, nrows): an int32 device tensor over the buffer."""
+        return self.dev()[:self.ncols * self.ld].reshape(self.ncols, self.ld)[:, :self.nrows]
+
+    def rows(self):
+        """The block on the host, (nrows, ncols)."""
+        return self.cols().cpu().numpy().T
+
+    def untouched(self):
+        return bool((self.buf == SENT32).all())
+
+    def assert_clean(self):
+        v = self.dev()
+        body = v[:self.ncols * self.ld].reshape(self.ncols, self.ld)
+        assert bool((body[:, self.nrows:] == SENT32).all()), "a gap row was written"
+        assert bool((v[self.ncols * self.ld:] == SENT32).all()), "the column after the last was written"
+        assert bool((self.buf[:self.lo] == SENT32).all()) and bool((self.buf[self.lo + self.n:] == SENT32).all()), \
+            "a write outside the block"
+
+    def assert_equal(self, ref, what=""):
+        """assert_clean, and the block equals the (nrows, ncols) host integer array `ref`."""
+        torch = _torch()
+        self.assert_clean()
+        ref = np.asarray(ref)
+        assert ref.shape == (self.nrows, self.ncols), (ref.shape, self.nrows, self.ncols)
+        want = torch.from_numpy(np.ascontiguousarray(ref.T).astype(np.int32)).to(self.buf.device)
+        ne = self.cols() != want
+        if bool(ne.any()):
+            c, r = (int(x) for x in torch.nonzero(ne)[0])
+            raise AssertionError(f"{what}: {int(ne.sum())} of {ne.numel()} elements differ, first at row {r} column {c}: "
+                                 f"got {int(self.cols()[c, r])}, want {int(want[c, r])}")
 
 
 class Flag:
