@@ -193,7 +193,7 @@ struct Step4Lanes {
   hipStream_t ss[kStep4MaxStreams];
   Step4Column cb[kStep4MaxStreams];
   uint32_t* codes[kStep4MaxStreams];
-  std::vector<hipEvent_t> events;
+  StreamOrder events;
   Step4Lanes(int64_t n, void* column_ws, void* codes_ws, hipStream_t s_, int max_lanes = kStep4MaxStreams) : s(s_) {
     ns = step4_streams() < max_lanes ? step4_streams() : max_lanes;
     for (int i = 0; i < ns; ++i) {
@@ -203,18 +203,7 @@ struct Step4Lanes {
       if (!ss[i]) ss[i] = s;
     }
   }
-  ~Step4Lanes() {
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-  }
-  int order(hipStream_t from, hipStream_t to) {  // `to` continues after `from`'s work so far
-    if (from == to) return PBH_OK;
-    hipEvent_t e = nullptr;
-    PBH_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    events.push_back(e);
-    PBH_CHECK_HIP(hipEventRecord(e, from));
-    PBH_CHECK_HIP(hipStreamWaitEvent(to, e, 0));
-    return PBH_OK;
-  }
+  int order(hipStream_t from, hipStream_t to) { return events.order(from, to); }
   int begin() {
     for (int i = 0; i < ns; ++i) {
       int st = order(s, ss[i]);
@@ -287,13 +276,7 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
   // the generated columns' inverse-CDF setups (tables built once, for step 1 and step 4);
   // declared before the guard below, so that on every return the tables are freed (stream
   // ordered, on s) only after the guard has synchronised the side streams that read them
-  struct Gens {
-    std::vector<GenColumn*> g;
-    hipStream_t s;
-    ~Gens() {
-      for (GenColumn* x : g) gen_destroy(x, s);
-    }
-  } gens{std::vector<GenColumn*>(a->columns ? k : 0, nullptr), s};
+  std::vector<GenHandle> gens(a->columns ? k : 0);
   struct SyncOnExit {
     hipStream_t s;
     bool side = false;
@@ -317,8 +300,8 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
   // demand), then one readback for all of them (instead of a stream sync per column).
   std::vector<char> have_sx(k, 0);  // sorted_x column c holds sort(X[:, c])
   auto materialise = [&](int c) -> int {  // sort(X[:, c]) into the workspace, once
-    if (have_sx[c] || !a->columns || !gens.g[c]) return PBH_OK;
-    int r = gen_sorted(gens.g[c], 0, n, L.sorted_x + (int64_t)c * n, nullptr, nullptr, s);
+    if (have_sx[c] || !a->columns || !gens[c].get()) return PBH_OK;
+    int r = gen_sorted(gens[c].get(), 0, n, L.sorted_x + (int64_t)c * n, nullptr, nullptr, s);
     if (r == PBH_OK) have_sx[c] = 1;
     return r;
   };
@@ -333,14 +316,12 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
   auto count_deferred = [&](int c, hipStream_t cs_) -> int {
     double T = 0.0;
     uint32_t cap = 0;
-    if (!cert_on || !gen_cert_plan(gens.g[c], n, &T, &cap))  // no bound, or as costly as the count
-      return gen_sorted(gens.g[c], 0, n, nullptr, a->columns[c].nonfinite_flag, L.counts + 2 * c, cs_);
-    uint32_t* list = nullptr;
-    PBH_CHECK_HIP(hipMallocAsync((void**)&list, ((size_t)cap + 64) * 4, cs_));
-    int r = gen_certify(gens.g[c], 0, n, T, list, cap, list + cap, a->columns[c].nonfinite_flag, L.counts + 2 * c,
-                        cs_);
-    PBH_CHECK_HIP(hipFreeAsync(list, cs_));
-    return r;
+    if (!cert_on || !gen_cert_plan(gens[c].get(), n, &T, &cap))  // no bound, or as costly as the count
+      return gen_sorted(gens[c].get(), 0, n, nullptr, a->columns[c].nonfinite_flag, L.counts + 2 * c, cs_);
+    Scratch<uint32_t> list;
+    PBH_CHECK_HIP(list.get(((size_t)cap + 64) * 4, cs_));
+    return gen_certify(gens[c].get(), 0, n, T, list, cap, list + cap, a->columns[c].nonfinite_flag, L.counts + 2 * c,
+                       cs_);
   };
   if (a->columns && defer)
     for (int c = 0; c < k; ++c) any_deferred |= (deferred[c] = !gen_discrete(a->columns[c].dist)) != 0;
@@ -352,47 +333,33 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
     {
       const int nts = step4_streams();  // 1 in measurement mode (pbh_set_serial)
       // an early return below (a column's table or counts failing) leaves work queued on the side
-      // streams that reads the tables ~Gens frees: join them on every exit path
+      // streams that reads the tables `gens` gives back: join them on every exit path
       if (nts > 1) sync_on_exit.side = true;
       hipStream_t ts[kStep4MaxStreams];
-      std::vector<hipEvent_t> tev;
-      struct Cleanup {
-        std::vector<hipEvent_t>& v;
-        ~Cleanup() {
-          for (hipEvent_t e : v) (void)hipEventDestroy(e);
-        }
-      } cleanup{tev};
-      auto order = [&](hipStream_t from, hipStream_t to) -> int {
-        if (from == to) return PBH_OK;
-        hipEvent_t e = nullptr;
-        PBH_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        tev.push_back(e);
-        PBH_CHECK_HIP(hipEventRecord(e, from));
-        PBH_CHECK_HIP(hipStreamWaitEvent(to, e, 0));
-        return PBH_OK;
-      };
+      StreamOrder fan;
       for (int i = 0; i < nts; ++i) {
         ts[i] = nts > 1 ? step4_side_stream(i) : s;
         if (!ts[i]) ts[i] = s;
-        if ((st = order(s, ts[i]))) return st;
+        if ((st = fan.order(s, ts[i]))) return st;
       }
       for (int c = 0; c < k; ++c) {
         const pbh_ic_column& g = a->columns[c];
         pbh_param prm[4];
         for (int j = 0; j < 4; ++j) prm[j] = pbh_param{nullptr, g.params[j]};
-        st = gen_create(g.seed, n, g.lhs_col, g.dist, prm, g.nparams, &gens.g[c], ts[c % nts]);
+        st = gen_create(g.seed, n, g.lhs_col, g.dist, prm, g.nparams, &gens[c], ts[c % nts]);
         if (st) return st;
+        gens[c].get_deleter().s = s;  // built on its lane, given back on s (after the lanes are joined)
         if (deferred[c]) continue;  // counted next to steps 1-3 (below)
         // run heads only for a discrete column (few runs); a continuous one ties rarely, if ever,
         // and would append every stratum (on the stream that built the column's table)
         const bool discrete = gen_discrete(g.dist);
-        st = gen_sorted(gens.g[c], 0, n, nullptr, g.nonfinite_flag, L.counts + 2 * c, ts[c % nts],
+        st = gen_sorted(gens[c].get(), 0, n, nullptr, g.nonfinite_flag, L.counts + 2 * c, ts[c % nts],
                         discrete ? L.heads_all + (int64_t)c * kHeadsCap : nullptr, discrete ? L.hcur + c : nullptr,
                         discrete ? kHeadsCap : 0);
         if (st) return st;
       }
       for (int i = 0; i < nts; ++i)
-        if ((st = order(ts[i], s))) return st;
+        if ((st = fan.order(ts[i], s))) return st;
     }
     PBH_CHECK_HIP(hipMemcpyAsync(cnt_host.data(), L.counts, 16 * (size_t)k, hipMemcpyDeviceToHost, s));
     PBH_CHECK_HIP(hipStreamSynchronize(s));
@@ -485,7 +452,7 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
           if (gen_discrete(a->columns[c].dist) && nheads <= cap) {  // appended heads, put in order
             heads = L.heads_all + (int64_t)c * kHeadsCap;
             st = sort_heads(heads, nheads, s);
-            if (!st) st = gen_set_runs(gens.g[c], heads, nheads, s);  // step 4 reads each run's value
+            if (!st) st = gen_set_runs(gens[c].get(), heads, nheads, s);  // step 4 reads each run's value
           } else {  // too many distinct values for the list: from the materialised column
             heads = (uint32_t*)L.tmp;
             st = materialise(c);
@@ -689,7 +656,7 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
       int buf = 0;
       st = step4_gen_place_passes(c, n, sh, lanes.cb[i], cs_, &buf);
       if (st) return st;
-      st = gen_place(gens.g[c], lanes.cb[i].pairs[buf], n, a->Y + (int64_t)c * a->y_cs, a->y_rs,
+      st = gen_place(gens[c].get(), lanes.cb[i].pairs[buf], n, a->Y + (int64_t)c * a->y_cs, a->y_rs,
                      a->idx_out ? a->idx_out + (int64_t)c * n : nullptr, sh.flags + c, cs_);
       if (st) return st;
     }
@@ -716,16 +683,9 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
     }
   } else {
     // The code histograms of all columns up front, one readback for the bucket-path decisions.
-    struct AsyncBuf {  // freed on every return (stream-ordered, before the guard's final sync)
-      uint32_t* p = nullptr;
-      hipStream_t s;
-      ~AsyncBuf() {
-        if (p) (void)hipFreeAsync(p, s);
-      }
-    } hb{nullptr, s};
-    uint32_t*& hists = hb.p;
+    Scratch<uint32_t> hists;  // freed on every return (stream-ordered, before the guard's final sync)
     if (code_buckets_enabled(n)) {
-      PBH_CHECK_HIP(hipMallocAsync((void**)&hists, (size_t)k * 1024 * 4, s));
+      PBH_CHECK_HIP(hists.get((size_t)k * 1024 * 4, s));
       for (int c = 0; c < k; ++c) {
         st = code_hist(L.codes + (int64_t)c * n, n, hists + (size_t)c * 1024, s);
         if (st) return st;
@@ -805,7 +765,7 @@ int ic_run(const pbh_ic_args* a, void* stream, int defer) {
 struct pbh_ic_owned {
   int m = 0;
   int64_t n = 0;
-  std::vector<GenColumn*> gens;
+  std::vector<GenHandle> gens;
   Step4Shared sh;
   Step4Lanes* lanes = nullptr;
   ReorderWs rw;
@@ -861,7 +821,7 @@ extern "C" int pbh_ic_owned_create(const pbh_ic_column* columns, int32_t m, int6
   pbh_ic_owned* h = new pbh_ic_owned();
   h->m = m;
   h->n = n;
-  h->gens.assign(m, nullptr);
+  h->gens.resize(m);
   h->cs.assign(m, nullptr);
   h->y.assign(m, nullptr);
   h->y_rs.assign(m, 1);
@@ -885,7 +845,7 @@ extern "C" int pbh_ic_owned_create(const pbh_ic_column* columns, int32_t m, int6
   }
   if (st != PBH_OK) {
     (void)hipStreamSynchronize(s);
-    for (GenColumn* g : h->gens) gen_destroy(g, s);
+    h->gens.clear();
     delete h->lanes;
     delete h;
     return st;
@@ -915,7 +875,7 @@ extern "C" int pbh_ic_owned_column(pbh_ic_owned* h, int32_t i, const double* cs,
   if (!st) st = step4_gen_place_passes(i, n, h->sh, L.cb[j], ls, &buf);
   if (!st)
     st = p_out ? place_positions(L.cb[j].pairs[buf], n, p_out, h->sh.flags + i, ls)
-               : gen_place(h->gens[i], L.cb[j].pairs[buf], n, y, y_rs, nullptr, h->sh.flags + i, ls);
+               : gen_place(h->gens[i].get(), L.cb[j].pairs[buf], n, y, y_rs, nullptr, h->sh.flags + i, ls);
   if (st) return st;
   if (done_event) PBH_CHECK_HIP(hipEventRecord((hipEvent_t)done_event, ls));
   h->cs[i] = cs;
@@ -940,7 +900,7 @@ extern "C" int pbh_ic_owned_finish(pbh_ic_owned* h, int32_t* redone_host, void* 
     if (redone_host) redone_host[i] = redo ? 1 : 0;
     if (!redo) continue;
     // the general path: sort(X) materialised, the column ranked by the code sort
-    st = gen_sorted(h->gens[i], 0, h->n, h->tmp, nullptr, nullptr, s);
+    st = gen_sorted(h->gens[i].get(), 0, h->n, h->tmp, nullptr, nullptr, s);
     if (!st && h->p_out[i])  // the positions: rank - 1 of every row (its Y is not needed)
       st = reorder_column(h->cs[i], h->n, h->tmp, h->tmp2, 1, (int32_t*)h->p_out[i], h->rw, s);
     else if (!st)
@@ -965,7 +925,8 @@ extern "C" int pbh_ic_owned_destroy(pbh_ic_owned* h, void* stream) {
   if (!h) return PBH_OK;
   hipStream_t s = as_stream(stream);
   if (h->lanes) (void)h->lanes->join(s);  // no lane may still read the tables being freed
-  for (GenColumn* g : h->gens) gen_destroy(g, s);
+  for (GenHandle& g : h->gens) g.get_deleter().s = s;
+  h->gens.clear();
   (void)hipStreamSynchronize(s);
   delete h->lanes;
   delete h;

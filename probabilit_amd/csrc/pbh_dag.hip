@@ -35,6 +35,7 @@
 #include "pbh_ops.h"
 #include "pbh_ppf_core.h"
 #include "pbh_rng.h"
+#include "pbh_scope.h"
 #include "pbh_timing.h"
 
 namespace pbh {
@@ -367,8 +368,8 @@ extern "C" int pbh_dag_eval(const pbh_dag_op* ops_host, int nops, const pbh_dag_
   const size_t b_tab = (size_t)nsobol * 1024 * 4;
   std::vector<uint8_t> host(b_ops + b_src + b_vec + b_tab, 0);
   hipStream_t st = as_stream(stream);
-  uint8_t* dev = nullptr;
-  PBH_CHECK_HIP(hipMallocAsync((void**)&dev, host.size(), st));
+  Scratch<uint8_t> dev;  // freed stream-ordered: after the kernel
+  PBH_CHECK_HIP(dev.get(host.size(), st));
   DagSrc* hs = (DagSrc*)(host.data() + b_ops);
   uint32_t* ht = (uint32_t*)(host.data() + b_ops + b_src + b_vec);
   const uint32_t* dt = (const uint32_t*)(dev + b_ops + b_src + b_vec);
@@ -419,22 +420,19 @@ extern "C" int pbh_dag_eval(const pbh_dag_op* ops_host, int nops, const pbh_dag_
     hp[k] = d;
   }
   if (nvectors) memcpy(host.data() + b_ops + b_src, vectors_host, (size_t)nvectors * sizeof(double*));
-  int rc = PBH_OK;
   if (hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, st) != hipSuccess) {
     set_error("pbh_dag_eval: upload failed");
-    rc = PBH_ERR_HIP;
-  } else {
-    const DOp* prog = (const DOp*)dev;
-    const DagSrc* srcs = (const DagSrc*)(dev + b_ops);
-    double* const* vecs = (double* const*)(dev + b_ops + b_src);
-    dim3 g(grid_for(n, kDTile, 256 * 16)), b(kDBlock);
-    const size_t lds = (size_t)nregs * kDTile * sizeof(double);
-    PBH_TIMED(kKDag, st, hipLaunchKernelGGL(k_dag, g, b, lds, st, prog, nops, srcs, vecs, row0, n, flags));
-    if (hipGetLastError() != hipSuccess) {
-      set_error("pbh_dag_eval: launch failed");
-      rc = PBH_ERR_HIP;
-    }
+    return PBH_ERR_HIP;
   }
-  PBH_CHECK_HIP(hipFreeAsync(dev, st));
-  return rc;
+  const DOp* prog = (const DOp*)dev.get();
+  const DagSrc* srcs = (const DagSrc*)(dev + b_ops);
+  double* const* vecs = (double* const*)(dev + b_ops + b_src);
+  dim3 g(grid_for(n, kDTile, 256 * 16)), b(kDBlock);
+  const size_t lds = (size_t)nregs * kDTile * sizeof(double);
+  PBH_TIMED(kKDag, st, hipLaunchKernelGGL(k_dag, g, b, lds, st, prog, nops, srcs, vecs, row0, n, flags));
+  if (hipGetLastError() != hipSuccess) {
+    set_error("pbh_dag_eval: launch failed");
+    return PBH_ERR_HIP;
+  }
+  return PBH_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "pbh_error.h"
 #include "pbh_ic.h"
+#include "pbh_scope.h"
 #include "pbh_special.h"
 #include "pbh_timing.h"
 
@@ -886,8 +887,8 @@ int apply_decorrelate_correlate(double* S, int64_t n, int k, int64_t ld, const d
   CodeMap c = cm ? *cm : CodeMap{};
   if (!cm) codes = nullptr;
   if (k <= 32) {
-    double* M = nullptr;
-    PBH_CHECK_HIP(hipMallocAsync((void**)&M, 32 * 32 * sizeof(double), s));
+    Scratch<double> M;  // freed stream-ordered: after the apply kernel
+    PBH_CHECK_HIP(M.get(32 * 32 * sizeof(double), s));
     hipLaunchKernelGGL(k_transform_matrix, dim3(1), dim3(64), 0, s, L, inv_diag, P, k, M);
     PBH_CHECK_LAUNCH();
     static const int rows = [] {  // 32 (default): 15.1 against 15.3-15.7 ms per step with 64
@@ -925,7 +926,6 @@ int apply_decorrelate_correlate(double* S, int64_t n, int k, int64_t ld, const d
       PBH_TIMED(kKApply, s,
                 hipLaunchKernelGGL(k_apply_mfma<64>, dim3(gb > 0 ? gb : 1), b, 0, s, S, n, k, ld, M, codes, ldc, c));
     PBH_CHECK_LAUNCH();
-    PBH_CHECK_HIP(hipFreeAsync(M, s));
     return PBH_OK;
   }
   if (k <= 8)

@@ -38,6 +38,7 @@
 
 #include "pbh_error.h"
 #include "pbh_lhs_dev.h"
+#include "pbh_scope.h"
 #include "pbh_sort.h"
 #include "probabilit_hip.h"
 #include "pbh_timing.h"
@@ -526,21 +527,15 @@ Pinned& pinned() {
   return p;
 }
 
-struct DevBufs {
-  hipStream_t s;
-  std::vector<void*> v;
-  template <class T>
-  int get(T** p, size_t count) {
-    void* x = nullptr;
-    PBH_CHECK_HIP(hipMallocAsync(&x, std::max<size_t>(count * sizeof(T), 256), s));
-    v.push_back(x);
-    *p = (T*)x;
-    return PBH_OK;
-  }
-  ~DevBufs() {
-    for (void* x : v) (void)hipFreeAsync(x, s);
-  }
-};
+// one more of a call's device buffers: count elements (at least 256 bytes), freed with `bufs`
+using CallBufs = std::vector<Scratch<void>>;
+template <class T>
+int dev_buf(CallBufs& bufs, T** p, size_t count, hipStream_t s) {
+  bufs.emplace_back();
+  PBH_CHECK_HIP(bufs.back().get(std::max<size_t>(count * sizeof(T), 256), s));
+  *p = (T*)bufs.back().get();
+  return PBH_OK;
+}
 
 // the stream the permutations are built on, behind the decode (one per process)
 hipStream_t perm_stream(hipStream_t fallback) {
@@ -552,7 +547,7 @@ hipStream_t perm_stream(hipStream_t fallback) {
   return st ? st : fallback;
 }
 
-// the caller's stream waits for the side stream on every exit (before DevBufs frees)
+// the caller's stream waits for the side stream on every exit (before the call's buffers are freed)
 struct SideJoin {
   hipStream_t side, main;
   hipEvent_t ev = nullptr;
@@ -606,7 +601,7 @@ int decode_attempt(const DecParams& base, const uint64_t* state_host, const uint
   pr.nb = pr.tcap / kBlk;
   pr.nband = (int64_t)band.size() / 2;
   const int64_t cap = std::min<int64_t>(pr.tcap, (int64_t)1 << 22);
-  DevBufs b{s};
+  CallBufs b;
   uint32_t *W, *tot, *pre, *tot2, *pre2;
   uint8_t *cls, *dec;
   uint2* list;
@@ -617,12 +612,14 @@ int decode_attempt(const DecParams& base, const uint64_t* state_host, const uint
   PermBufs pb;
   char* sort_ws;
   int st;
-  if ((st = b.get(&W, pr.tcap)) || (st = b.get(&cls, pr.tcap)) || (st = b.get(&tot, 2 * pr.nb)) ||
-      (st = b.get(&pre, 2 * (pr.nb + 1))) || (st = b.get(&tot2, pr.nb)) || (st = b.get(&pre2, pr.nb + 1)) ||
-      (st = b.get(&list, cap)) || (st = b.get(&dec, cap)) || (st = b.get(&band_dev, pr.nband)) ||
-      (st = b.get(&P, d + 1)) || (st = b.get(&err, 1)) || (st = b.get(&okc, d)) || (st = b.get(&pcg_ws, 128)) ||
-      (st = b.get(&pb.S, n)) || (st = b.get(&pb.M, n)) ||
-      (st = b.get(&sort_ws, sort_workspace_bytes(n))))
+  if ((st = dev_buf(b, &W, pr.tcap, s)) || (st = dev_buf(b, &cls, pr.tcap, s)) ||
+      (st = dev_buf(b, &tot, 2 * pr.nb, s)) || (st = dev_buf(b, &pre, 2 * (pr.nb + 1), s)) ||
+      (st = dev_buf(b, &tot2, pr.nb, s)) || (st = dev_buf(b, &pre2, pr.nb + 1, s)) ||
+      (st = dev_buf(b, &list, cap, s)) || (st = dev_buf(b, &dec, cap, s)) ||
+      (st = dev_buf(b, &band_dev, pr.nband, s)) || (st = dev_buf(b, &P, d + 1, s)) || (st = dev_buf(b, &err, 1, s)) ||
+      (st = dev_buf(b, &okc, d, s)) || (st = dev_buf(b, &pcg_ws, 128, s)) ||
+      (st = dev_buf(b, &pb.S, n, s)) || (st = dev_buf(b, &pb.M, n, s)) ||
+      (st = dev_buf(b, &sort_ws, sort_workspace_bytes(n), s)))
     return st;
   sort_carve(sort_ws, n, pb.sb);
   const hipStream_t side = perm_stream(s);
@@ -737,9 +734,9 @@ int lhs_reference_device(const uint64_t* state_host, const uint64_t* inc_host, b
   const u128 inc = ((u128)inc_host[1] << 64) | inc_host[0];
   int st;
   if (n == 1) {
-    DevBufs b{s};
+    CallBufs b;
     u128* pcg_ws;
-    if ((st = b.get(&pcg_ws, 128))) return st;
+    if ((st = dev_buf(b, &pcg_ws, 128, s))) return st;
     if ((st = pbh_pcg64_random(state_host, inc_host, 0, 1, d, q, ldq, pcg_ws, 128 * sizeof(u128), s))) return st;
     hipLaunchKernelGGL(k_single_row, dim3(1), dim3(256), 0, s, q, ldq, d);
     PBH_CHECK_LAUNCH();
@@ -748,9 +745,9 @@ int lhs_reference_device(const uint64_t* state_host, const uint64_t* inc_host, b
   } else {
     std::vector<u128> table(128);
     pcg::jump_table(inc, table.data());
-    DevBufs b{s};
+    CallBufs b;
     u128* jt;
-    if ((st = b.get(&jt, 128))) return st;
+    if ((st = dev_buf(b, &jt, 128, s))) return st;
     PBH_CHECK_HIP(hipMemcpyAsync(jt, table.data(), 128 * sizeof(u128), hipMemcpyHostToDevice, s));
     DecParams pr{};
     pr.s_lo = (uint64_t)s0;

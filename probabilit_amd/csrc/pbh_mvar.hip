@@ -20,7 +20,6 @@
 #include "pbh_error.h"
 #include "pbh_mvar.h"
 #include "pbh_ppf_ext.h"
-#include "pbh_table_cache.h"
 
 namespace pbh {
 namespace {
@@ -92,17 +91,15 @@ int tile_rows(int d, size_t fixed) {
   return R > kMvarMaxBlock ? kMvarMaxBlock : R;
 }
 
-// a stream-ordered device copy of a host table (freed by hipFreeAsync after the launch).  The
+// a stream-ordered device copy of a host table (freed stream-ordered, after the launch).  The
 // host side is the caller's (or this call's) pageable memory, so the copy is waited for: the
 // table is a few KiB and the Python layer has just read q[0] on this stream anyway.
-int upload(const void* host, size_t bytes, void** dev, hipStream_t s) {
-  *dev = nullptr;
-  PBH_CHECK_HIP(hipMallocAsync(dev, bytes, s));
-  hipError_t e = hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, s);
+int upload(const void* host, size_t bytes, Scratch<void>& dev, hipStream_t s) {
+  PBH_CHECK_HIP(dev.get(bytes, s));
+  hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
-    (void)hipFreeAsync(*dev, s);
-    *dev = nullptr;
+    dev.reset();
     set_error("hipMemcpyAsync of a parameter table failed: %s", hipGetErrorString(e));
     return PBH_ERR_HIP;
   }
@@ -138,9 +135,9 @@ extern "C" int pbh_multivariate_normal(uint64_t seed, int64_t row0, int64_t nrow
     h[c] = mean_host[c];
     for (int j = 0; j < d; ++j) h[(size_t)dp + (size_t)j * dp + c] = a_host[(size_t)c * d + j];
   }
-  void* dev = nullptr;
-  if (int st = upload(h.data(), h.size() * sizeof(double), &dev, s)) return st;
-  const double* mean = (const double*)dev;
+  Scratch<void> dev;
+  if (int st = upload(h.data(), h.size() * sizeof(double), dev, s)) return st;
+  const double* mean = (const double*)dev.get();
   const double* At = mean + dp;
   const size_t abytes = (size_t)d * dp * sizeof(double);
   const bool a_lds = abytes + (size_t)kWave * d * sizeof(double) <= (size_t)kMvarLds;
@@ -151,9 +148,7 @@ extern "C" int pbh_multivariate_normal(uint64_t seed, int64_t row0, int64_t nrow
     hipLaunchKernelGGL(k_mvn<true>, g, b, lds, s, seed, row0, nrows, (int)d, mean, At, out, ld, nonfinite_flag);
   else
     hipLaunchKernelGGL(k_mvn<false>, g, b, lds, s, seed, row0, nrows, (int)d, mean, At, out, ld, nonfinite_flag);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(dev, s);
-  PBH_CHECK_HIP(e);
+  PBH_CHECK_LAUNCH();
   return PBH_OK;
 }
 
@@ -168,30 +163,20 @@ extern "C" int pbh_dirichlet(uint64_t seed, int64_t row0, int64_t nrows, int32_t
   hipStream_t s = as_stream(stream);
   // one guide per distinct shape (the process cache's when it has room); a shape whose guide
   // cannot be had takes plain igami
-  std::map<double, double*> guides;
+  std::map<double, TableRef> guides;
   std::vector<mvar::GammaComp> comp((size_t)d);
   for (int j = 0; j < d; ++j) {
     const double a = alpha_host[j];
     auto it = guides.find(a);
     if (it == guides.end()) it = guides.emplace(a, gamma_guide_table(a, s)).first;
-    comp[j] = mvar::GammaComp{a, sf::gamma_aux(a), it->second};
+    comp[j] = mvar::GammaComp{a, sf::gamma_aux(a), it->second.get()};
   }
-  auto release = [&]() {
-    for (auto& kv : guides)
-      if (kv.second) release_table(kv.second, s);
-  };
-  void* dev = nullptr;
-  if (int st = upload(comp.data(), comp.size() * sizeof(mvar::GammaComp), &dev, s)) {
-    release();
-    return st;
-  }
+  Scratch<void> dev;  // (freed before the guides are given back)
+  if (int st = upload(comp.data(), comp.size() * sizeof(mvar::GammaComp), dev, s)) return st;
   const int R = tile_rows(d, 0);
   hipLaunchKernelGGL(k_dirichlet, dim3(tile_grid(nrows, R)), dim3((unsigned)R), (size_t)R * d * sizeof(double), s, seed,
-                     row0, nrows, (int)d, (const mvar::GammaComp*)dev, out, ld, nonfinite_flag);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(dev, s);
-  release();
-  PBH_CHECK_HIP(e);
+                     row0, nrows, (int)d, (const mvar::GammaComp*)dev.get(), out, ld, nonfinite_flag);
+  PBH_CHECK_LAUNCH();
   return PBH_OK;
 }
 
@@ -205,12 +190,10 @@ extern "C" int pbh_multinomial(uint64_t seed, int64_t row0, int64_t nrows, int32
     PBH_REQUIRE(pc_host[j] >= 0.0 && pc_host[j] <= 1.0, "pbh_multinomial: pc[%d] = %g is outside [0, 1]", j, pc_host[j]);
   if (nrows == 0) return PBH_OK;
   hipStream_t s = as_stream(stream);
-  void* dev = nullptr;
-  if (int st = upload(pc_host, (size_t)d * sizeof(double), &dev, s)) return st;
+  Scratch<void> dev;
+  if (int st = upload(pc_host, (size_t)d * sizeof(double), dev, s)) return st;
   hipLaunchKernelGGL(k_multinomial, dim3(grid_for(nrows, kMvarMaxBlock, 8192)), dim3(kMvarMaxBlock), 0, s, seed, row0,
-                     nrows, (int)d, n, (const double*)dev, out, ld);
-  const hipError_t e = hipGetLastError();
-  (void)hipFreeAsync(dev, s);
-  PBH_CHECK_HIP(e);
+                     nrows, (int)d, n, (const double*)dev.get(), out, ld);
+  PBH_CHECK_LAUNCH();
   return PBH_OK;
 }

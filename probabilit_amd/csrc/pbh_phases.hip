@@ -195,21 +195,17 @@ extern "C" int pbh_lhs_sorted_counts(uint64_t seed, int64_t n, int64_t t0, int64
   hipStream_t s = as_stream(stream);
   pbh_param prm[4];
   for (int j = 0; j < nparams; ++j) prm[j] = pbh_param{nullptr, params_host[j]};
-  GenColumn* g = nullptr;
+  GenHandle g;  // stream-ordered: the tables are freed after the kernel
   int st = gen_create(seed, n, col, dist, prm, nparams, &g, s);
   if (st != PBH_OK) return st;
   double T = 0.0;
   uint32_t cap = 0;
-  if (certify && !heads && gen_cert_plan(g, nt, &T, &cap)) {  // the certificate; else the exact counts
-    uint32_t* list = nullptr;
-    PBH_CHECK_HIP(hipMallocAsync((void**)&list, ((size_t)cap + 64) * 4, s));
-    st = gen_certify(g, t0, nt, T, list, cap, list + cap, nonfinite_flag, counts, s);
-    PBH_CHECK_HIP(hipFreeAsync(list, s));
-  } else {
-    st = gen_sorted(g, t0, nt, nullptr, nonfinite_flag, counts, s, heads, hcur, heads ? hcap : 0);
+  if (certify && !heads && gen_cert_plan(g.get(), nt, &T, &cap)) {  // the certificate; else the exact counts
+    Scratch<uint32_t> list;
+    PBH_CHECK_HIP(list.get(((size_t)cap + 64) * 4, s));
+    return gen_certify(g.get(), t0, nt, T, list, cap, list + cap, nonfinite_flag, counts, s);
   }
-  gen_destroy(g, s);  // stream-ordered: the tables are freed after the kernel
-  return st;
+  return gen_sorted(g.get(), t0, nt, nullptr, nonfinite_flag, counts, s, heads, hcur, heads ? hcap : 0);
 }
 
 extern "C" int pbh_lhs_values_at(const pbh_ic_column* column, int64_t n, const uint32_t* p, int64_t m, double* y,
@@ -220,12 +216,10 @@ extern "C" int pbh_lhs_values_at(const pbh_ic_column* column, int64_t n, const u
   hipStream_t s = as_stream(stream);
   pbh_param prm[4];
   for (int j = 0; j < 4; ++j) prm[j] = pbh_param{nullptr, column->params[j]};
-  GenColumn* g = nullptr;
+  GenHandle g;
   int st = gen_create(column->seed, n, column->lhs_col, column->dist, prm, column->nparams, &g, s);
   if (st != PBH_OK) return st;
-  st = gen_values_at(g, p, m, y, y_rs, s);
-  gen_destroy(g, s);
-  return st;
+  return gen_values_at(g.get(), p, m, y, y_rs, s);
 }
 
 extern "C" int pbh_sort_heads(uint32_t* heads, int64_t nh, void* stream) {

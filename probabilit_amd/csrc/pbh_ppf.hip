@@ -1235,13 +1235,8 @@ int launch_poisson_lds(const double* q, int64_t qs, int64_t n, const GammaLhs* l
                        const PoissonTable& pt, double* out, int32_t* flag, hipStream_t s) {
   if (n <= 0) return PBH_OK;
   const uint32_t cap = (uint32_t)((n >> 10) + 4096 < (1u << 30) ? (n >> 10) + 4096 : (1u << 30));
-  unsigned long long* slow = nullptr;
-  PBH_CHECK_HIP(hipMallocAsync((void**)&slow, ((size_t)cap + 1) * 8, s));
-  struct Free {
-    unsigned long long* p;
-    hipStream_t s;
-    ~Free() { (void)hipFreeAsync(p, s); }  // stream-ordered: after the slow kernel
-  } fr{slow, s};
+  Scratch<unsigned long long> slow;  // freed stream-ordered: after the slow kernel
+  PBH_CHECK_HIP(slow.get(((size_t)cap + 1) * 8, s));
   PBH_CHECK_HIP(hipMemsetAsync(slow, 0, 8, s));
   const GammaLhs l = lc ? *lc : GammaLhs{0, 1, 0, 0};
   const dim3 b(kBlock);
@@ -1273,14 +1268,13 @@ bool launch_gamma_w(const double* q, int64_t qs, int64_t n, const GammaLhs* lc, 
   if (!gamma_win_on() || !gamma_window_w(kGSweepW, pt.guide, kGWin, &j0, &jn)) return false;
   if (n <= 0) return true;
   const uint32_t cap = (uint32_t)((n >> 8) + 4096 < (1u << 30) ? (n >> 8) + 4096 : (1u << 30));
-  unsigned long long* slow = nullptr;
-  if (hipMallocAsync((void**)&slow, ((size_t)cap + 1) * 8, s) != hipSuccess) {
+  Scratch<unsigned long long> slow;  // freed stream-ordered: after the slow kernel
+  if (slow.get(((size_t)cap + 1) * 8, s) != hipSuccess) {
     *status = PBH_ERR_HIP;
     set_error("pbh_ppf: hipMallocAsync of the gamma slow list failed");
     return true;
   }
   if (hipMemsetAsync(slow, 0, 8, s) != hipSuccess) {
-    (void)hipFreeAsync(slow, s);
     *status = PBH_ERR_HIP;
     set_error("pbh_ppf: hipMemsetAsync failed");
     return true;
@@ -1302,7 +1296,6 @@ bool launch_gamma_w(const double* q, int64_t qs, int64_t n, const GammaLhs* lc, 
     });
   }
   if (hipGetLastError() != hipSuccess) *status = PBH_ERR_HIP;
-  (void)hipFreeAsync(slow, s);  // stream-ordered: after the slow kernel
   return true;
 }
 
@@ -1898,7 +1891,7 @@ int expected_nparams(int dist) {
 
 // Scalar-mu poisson: build the CDF table pdtr(k, mu), k in [k_lo, k_lo + len), in a
 // stream-ordered allocation; elements outside its coverage fall back to the search.
-int with_params(int dist, const pbh_param* params, int nparams, Params& prm, PoissonTable& pt, double** table,
+int with_params(int dist, const pbh_param* params, int nparams, Params& prm, PoissonTable& pt, TableRef& table,
                 hipStream_t s) {
   int want = expected_nparams(dist);
   if (want < 0) {
@@ -1912,16 +1905,16 @@ int with_params(int dist, const pbh_param* params, int nparams, Params& prm, Poi
     prm.val[j] = j < nparams ? params[j].value : 0.0;
   }
   pt = PoissonTable{};
-  *table = nullptr;
+  table.reset();
   if (dist == PBH_DIST_GAMMA && params[0].ptr == nullptr && params[0].value > 0.0 && isfinite(params[0].value)) {
     const double a = params[0].value;
     const int m = sf::kGammaGuideM;
-    *table = gamma_guide_table(a, s);
-    if (!*table) {
+    table = gamma_guide_table(a, s);
+    if (!table) {
       set_error("gamma guide table for a = %g failed", a);
       return PBH_ERR_HIP;
     }
-    double* tb = *table;
+    double* tb = table;
     pt.has_gamma = 1;
     pt.aux = sf::gamma_aux(a);
     pt.guide = sf::GammaGuide{tb, tb + m, tb + 2 * m, tb + 3 * m, m, sf::kGammaGuideZ0, sf::kGammaGuideH,
@@ -1944,17 +1937,14 @@ int with_params(int dist, const pbh_param* params, int nparams, Params& prm, Poi
                            (int32_t*)(t + 2 * len));
         return hipGetLastError() == hipSuccess;
       };
-      *table = cached_table(kTabPoisson, &mu, 1, bytes, s, build);
-      if (!*table) {
-        PBH_CHECK_HIP(hipMallocAsync((void**)table, bytes, s));
-        if (!build(*table, s)) {
-          set_error("poisson table launch failed");
-          return PBH_ERR_HIP;
-        }
+      table = acquire_table(kTabPoisson, &mu, 1, bytes, s, build);
+      if (!table) {
+        set_error("poisson table for mu = %g failed", mu);
+        return PBH_ERR_HIP;
       }
-      pt.cdf = *table;
-      pt.win = *table + len;
-      pt.cdf_guide = (int32_t*)(*table + 2 * len);
+      pt.cdf = table;
+      pt.win = table + len;
+      pt.cdf_guide = (int32_t*)(table + 2 * len);
       pt.k_lo = k_lo;
       pt.len = len;
     }
@@ -1967,9 +1957,9 @@ int with_params(int dist, const pbh_param* params, int nparams, Params& prm, Poi
 // The gamma guide of shape a (4 x kGammaGuideM doubles: y, d1, d2, ok), for gamma (with_params)
 // and the extended distributions whose ppf is gammaincinv (chi, maxwell, nakagami, chi2:
 // pbh_ppf_ext.hip): the process cache's (pbh_table_cache.hip), or a fresh stream-ordered
-// allocation when the cache is full; callers end with release_table.  NULL for an invalid a.
-double* gamma_guide_table(double a, hipStream_t s) {
-  if (!(a > 0.0 && isfinite(a))) return nullptr;
+// allocation when the cache is full.  Empty for an invalid a.
+TableRef gamma_guide_table(double a, hipStream_t s) {
+  if (!(a > 0.0 && isfinite(a))) return TableRef();
   const int m = sf::kGammaGuideM;
   auto build = [=](double* tb, hipStream_t st) {
     sf::GammaGuide T{tb, tb + m, tb + 2 * m, tb + 3 * m, m, sf::kGammaGuideZ0, sf::kGammaGuideH, 1.0 / sf::kGammaGuideH};
@@ -1979,14 +1969,7 @@ double* gamma_guide_table(double a, hipStream_t s) {
     return hipGetLastError() == hipSuccess;
   };
   const size_t bytes = (size_t)4 * m * sizeof(double);
-  if (double* t = cached_table(kTabGammaGuide, &a, 1, bytes, s, build)) return t;
-  double* tb = nullptr;
-  if (hipMallocAsync((void**)&tb, bytes, s) != hipSuccess) return nullptr;
-  if (!build(tb, s)) {
-    (void)hipFreeAsync(tb, s);
-    return nullptr;
-  }
-  return tb;
+  return acquire_table(kTabGammaGuide, &a, 1, bytes, s, build);
 }
 
 struct GenColumn {
@@ -1996,48 +1979,44 @@ struct GenColumn {
   int dist;
   Params prm;
   PoissonTable pt;
-  double* table;
+  TableRef table;
   bool ext;        // an extended distribution (pbh_ppf_ext.hip): its kernels take xval
   double xval[4];
   const uint32_t* rheads = nullptr;  // a discrete column's sorted run heads (gen_set_runs)
-  double* rvals = nullptr;           // the value of each run
+  Scratch<double> rvals;             // the value of each run
   int64_t nruns = 0;
 };
 
-int gen_create(uint64_t seed, int64_t n, int col, int dist, const pbh_param* params, int nparams, GenColumn** out,
+int gen_create(uint64_t seed, int64_t n, int col, int dist, const pbh_param* params, int nparams, GenHandle* out,
                hipStream_t s) {
   for (int j = 0; j < nparams; ++j)
     PBH_REQUIRE(params[j].ptr == nullptr, "stratum-ordered LHS generation needs scalar parameters");
-  GenColumn* g = new GenColumn{};
+  GenHandle g(new GenColumn{}, GenDelete{s});
   g->seed = seed;
   g->n = n;
   g->col = (uint32_t)col;
   g->dist = dist;
   if (const int want = ext_nparams(dist); want >= 0) {
     if (nparams != want || (nparams && !params)) {
-      delete g;
       set_error("distribution %d expects %d parameters, got %d", dist, want, nparams);
       return PBH_ERR_INVALID;
     }
     g->ext = true;
     for (int j = 0; j < nparams; ++j) g->xval[j] = params[j].value;
     g->table = ext_gen_table(dist, g->xval, nparams, s);
-    *out = g;
+    *out = std::move(g);
     return PBH_OK;
   }
-  int st = with_params(dist, params, nparams, g->prm, g->pt, &g->table, s);
-  if (st != PBH_OK) {
-    delete g;
-    return st;
-  }
-  *out = g;
+  int st = with_params(dist, params, nparams, g->prm, g->pt, g->table, s);
+  if (st != PBH_OK) return st;
+  *out = std::move(g);
   return PBH_OK;
 }
 
-void gen_destroy(GenColumn* g, hipStream_t s) {
-  if (!g) return;
-  release_table(g->table, s);
-  if (g->rvals) (void)hipFreeAsync(g->rvals, s);
+void GenDelete::operator()(GenColumn* g) const {  // the table and the run values leave on s
+  g->table.set_stream(s);
+  g->table.reset();
+  g->rvals.set_stream(s);
   delete g;
 }
 
@@ -2372,8 +2351,8 @@ static int place_launch(const GenColumn* g, const uint64_t* pairs, const uint32_
   if (gamma_win_on() && gamma_lds_ok(g->dist, g->prm, g->pt) && gamma_window(n, g->pt.guide, &j0, &jn)) {
     // the slow list: a counter and cap entries (stream-ordered, freed after the second kernel)
     const uint32_t cap = (uint32_t)(rows / 64 + 1024 < (1 << 20) ? rows / 64 + 1024 : (1 << 20));
-    unsigned long long* slow = nullptr;
-    PBH_CHECK_HIP(hipMallocAsync((void**)&slow, ((size_t)cap + 1) * 8, s));
+    Scratch<unsigned long long> slow;
+    PBH_CHECK_HIP(slow.get(((size_t)cap + 1) * 8, s));
     PBH_CHECK_HIP(hipMemsetAsync(slow, 0, 8, s));
     PBH_TIMED(kKPlaceGen, s,
               hipLaunchKernelGGL(k_place_gen_gamma_w<BYROW>, dim3((unsigned)(blocks < 512 ? blocks : 512)),
@@ -2383,7 +2362,6 @@ static int place_launch(const GenColumn* g, const uint64_t* pairs, const uint32_
     hipLaunchKernelGGL(k_place_gen_gamma_slow<BYROW>, dim3(PBH_SLOW_GRID), dim3(256), 0, s, pairs, pidx, rows, n, g->seed,
                        g->col, g->prm, g->pt, y, y_rs, state, slow, cap);
     PBH_CHECK_LAUNCH();
-    PBH_CHECK_HIP(hipFreeAsync(slow, s));
     return PBH_OK;
   }
   if (gamma_lds_ok(g->dist, g->prm, g->pt)) {
@@ -2451,15 +2429,12 @@ int gen_set_runs(GenColumn* g, const uint32_t* heads, int64_t nh, hipStream_t s)
     return !(e && e[0] == '0');
   }();
   if (!on || !gen_discrete(g->dist) || nh < 1 || nh > kRunsLdsMax || g->n < 1) return PBH_OK;
-  double* v = nullptr;
-  PBH_CHECK_HIP(hipMallocAsync((void**)&v, (size_t)nh * 8, s));
+  Scratch<double> v;
+  PBH_CHECK_HIP(v.get((size_t)nh * 8, s));
   const int st = gen_values_at(g, heads, nh, v, 1, s);  // the value of each run: its head's
-  if (st != PBH_OK) {
-    (void)hipFreeAsync(v, s);
-    return st;
-  }
-  if (g->rvals) (void)hipFreeAsync(g->rvals, s);
-  g->rvals = v;
+  if (st != PBH_OK) return st;
+  g->rvals.set_stream(s);  // earlier run values leave behind the kernels queued on s
+  g->rvals = std::move(v);
   g->rheads = heads;
   g->nruns = nh;
   return PBH_OK;
@@ -2470,12 +2445,10 @@ int lhs_sorted_ppf(uint64_t seed, int64_t n, int64_t t0, int64_t nt, int col, in
   PBH_REQUIRE(t0 >= 0 && nt >= 0 && t0 + nt <= n, "lhs_sorted_ppf: strata [%lld, %lld) outside [0, %lld)",
               (long long)t0, (long long)(t0 + nt), (long long)n);
   if (nt == 0) return PBH_OK;
-  GenColumn* g = nullptr;
+  GenHandle g;
   int st = gen_create(seed, n, col, dist, params, nparams, &g, s);
   if (st != PBH_OK) return st;
-  st = gen_sorted(g, t0, nt, out, flag, counts, s);
-  gen_destroy(g, s);
-  return st;
+  return gen_sorted(g.get(), t0, nt, out, flag, counts, s);
 }
 
 int sort_heads(uint32_t* heads, int64_t nh, hipStream_t s) {
@@ -2582,12 +2555,10 @@ extern "C" int pbh_ppf(int dist, const double* q, int64_t q_stride, int64_t n, c
   if (dist >= PBH_DIST_BETA) return ppf_ext(dist, q, q_stride, n, params, nparams, out, nonfinite_flag, s);
   Params prm;
   PoissonTable pt;
-  double* table = nullptr;
-  int st = with_params(dist, params, nparams, prm, pt, &table, s);
+  TableRef table;  // given back stream-ordered: after the kernels
+  int st = with_params(dist, params, nparams, prm, pt, table, s);
   if (st != PBH_OK) return st;
-  st = launch_ppf(dist, q, q_stride, n, prm, pt, out, nonfinite_flag, s);
-  release_table(table, s);
-  return st;
+  return launch_ppf(dist, q, q_stride, n, prm, pt, out, nonfinite_flag, s);
 }
 
 extern "C" int pbh_lhs_ppf(uint64_t seed, int64_t n, int64_t row0, int64_t nrows, int col, int dist,
@@ -2601,12 +2572,10 @@ extern "C" int pbh_lhs_ppf(uint64_t seed, int64_t n, int64_t row0, int64_t nrows
     return lhs_ppf_ext(seed, n, row0, nrows, col, dist, params, nparams, out, nonfinite_flag, s);
   Params prm;
   PoissonTable pt;
-  double* table = nullptr;
-  int st = with_params(dist, params, nparams, prm, pt, &table, s);
+  TableRef table;
+  int st = with_params(dist, params, nparams, prm, pt, table, s);
   if (st != PBH_OK) return st;
-  st = launch_lhs_ppf(dist, seed, n, row0, nrows, (uint32_t)col, prm, pt, out, nonfinite_flag, s);
-  release_table(table, s);
-  return st;
+  return launch_lhs_ppf(dist, seed, n, row0, nrows, (uint32_t)col, prm, pt, out, nonfinite_flag, s);
 }
 
 // Every column of a graph's uncorrelated native-LHS leaves in one call (round 5, cfg2): each
@@ -2622,44 +2591,31 @@ extern "C" int pbh_lhs_ppf_columns(const pbh_ic_column* cols, int32_t k, int64_t
   hipStream_t s = as_stream(stream);
   const int nts = step4_streams();  // 1 in the serial measurement mode
   hipStream_t ts[kStep4MaxStreams];
-  std::vector<hipEvent_t> ev;
-  struct Cleanup {
-    std::vector<hipEvent_t>& v;
-    bool joined = false;
-    ~Cleanup() {
-      if (!joined) step4_sync_side_streams();  // an error return: no lane may still read a table
-      for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
-  } cleanup{ev};
-  auto order = [&](hipStream_t from, hipStream_t to) -> int {
-    if (from == to) return PBH_OK;
-    hipEvent_t e = nullptr;
-    PBH_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ev.push_back(e);
-    PBH_CHECK_HIP(hipEventRecord(e, from));
-    PBH_CHECK_HIP(hipStreamWaitEvent(to, e, 0));
-    return PBH_OK;
-  };
+  StreamOrder lanes;
   // below 2^20 rows a column's kernel is a few microseconds: the lanes' events (create, record,
   // wait, destroy on each side) would cost more host time than the overlap saves, and the setup
   // tables are cached after the first call, so the columns go on the caller's stream in order
   const int nl = nrows < ((int64_t)1 << 20) ? 1 : (nts < k ? nts : k);
-  for (int i = 0; i < nl; ++i) {
-    ts[i] = nl > 1 ? step4_side_stream(i) : s;
-    if (!ts[i]) ts[i] = s;
-    if (int st = order(s, ts[i])) return st;
-  }
-  for (int c = 0; c < k; ++c) {
-    pbh_param prm[4];
-    for (int j = 0; j < 4; ++j) prm[j] = pbh_param{nullptr, cols[c].params[j]};
-    if (int st = pbh_lhs_ppf(cols[c].seed, n, row0, nrows, cols[c].lhs_col, cols[c].dist, prm, cols[c].nparams,
-                             out + (int64_t)c * ld, cols[c].nonfinite_flag, ts[c % nl]))
-      return st;
-  }
-  for (int i = 0; i < nl; ++i)
-    if (int st = order(ts[i], s)) return st;
-  cleanup.joined = true;
-  return PBH_OK;
+  auto run = [&]() -> int {
+    for (int i = 0; i < nl; ++i) {
+      ts[i] = nl > 1 ? step4_side_stream(i) : s;
+      if (!ts[i]) ts[i] = s;
+      if (int st = lanes.order(s, ts[i])) return st;
+    }
+    for (int c = 0; c < k; ++c) {
+      pbh_param prm[4];
+      for (int j = 0; j < 4; ++j) prm[j] = pbh_param{nullptr, cols[c].params[j]};
+      if (int st = pbh_lhs_ppf(cols[c].seed, n, row0, nrows, cols[c].lhs_col, cols[c].dist, prm, cols[c].nparams,
+                               out + (int64_t)c * ld, cols[c].nonfinite_flag, ts[c % nl]))
+        return st;
+    }
+    for (int i = 0; i < nl; ++i)
+      if (int st = lanes.order(ts[i], s)) return st;
+    return PBH_OK;
+  };
+  const int st = run();
+  if (st) step4_sync_side_streams();  // an error return: no lane may still read a table
+  return st;
 }
 
 extern "C" int pbh_fill_lhs(uint64_t seed, int64_t n, int64_t row0, int64_t nrows, int col0, int ncols,
@@ -2730,8 +2686,8 @@ extern "C" int pbh_sobol_ppf(const uint32_t* sv_host, const uint32_t* shift_host
   sc.scale = 1.0 / (double)((uint64_t)1 << bits);
   Params prm;
   PoissonTable pt;
-  double* table = nullptr;
-  int st = with_params(dist, params, nparams, prm, pt, &table, s);
+  TableRef table;
+  int st = with_params(dist, params, nparams, prm, pt, table, s);
   if (st != PBH_OK) return st;
   dim3 g(ppf_grid(nrows)), b(kBlock);
   switch (dist) {
@@ -2758,6 +2714,5 @@ extern "C" int pbh_sobol_ppf(const uint32_t* sv_host, const uint32_t* shift_host
       break;
   }
   PBH_CHECK_LAUNCH();
-  release_table(table, s);
   return PBH_OK;
 }

@@ -333,25 +333,25 @@ int discrete_table_len(int dist, const double* v) {
 // distribution has none): beta with scalar, valid (a, b) -> its guide; chi / maxwell / nakagami /
 // chi2 with a scalar shape -> gammaincinv's guide (pbh_ppf.hip gamma_guide_table); binom /
 // bernoulli / nbinom with scalar parameters -> [len, CDF (len), complement (len)]; the process
-// cache's (pbh_table_cache.hip) when it has room, callers end with release_table
-double* beta_guide_table(double a, double b, hipStream_t s);
+// cache's (pbh_table_cache.hip) when it has room
+TableRef beta_guide_table(double a, double b, hipStream_t s);
 
-double* build_table(int dist, const pbh_param* params, int nparams, hipStream_t s) {
+TableRef build_table(int dist, const pbh_param* params, int nparams, hipStream_t s) {
   if (dist == PBH_DIST_T) {  // stdtrit through I^-1(.; df / 2, 1 / 2): beta's guide of (df / 2, 1 / 2)
-    if (nparams < 1 || params[0].ptr) return nullptr;
+    if (nparams < 1 || params[0].ptr) return TableRef();
     const double df = params[0].value;
-    if (!(df > 0.0 && df < 1e5)) return nullptr;
+    if (!(df > 0.0 && df < 1e5)) return TableRef();
     return beta_guide_table(0.5 * df, 0.5, s);
   }
   if (is_gamma_family(dist) || dist == PBH_DIST_INVGAMMA) {
-    if (dist != PBH_DIST_MAXWELL && (nparams < 1 || params[0].ptr)) return nullptr;
+    if (dist != PBH_DIST_MAXWELL && (nparams < 1 || params[0].ptr)) return TableRef();
     return gamma_guide_table(gamma_family_a(dist, nparams ? params[0].value : 0.0), s);
   }
   if (dist == PBH_DIST_BETABINOM || dist == PBH_DIST_HYPERGEOM || dist == PBH_DIST_NHYPERGEOM) {
-    if (nparams < 3 || params[0].ptr || params[1].ptr || params[2].ptr) return nullptr;
+    if (nparams < 3 || params[0].ptr || params[1].ptr || params[2].ptr) return TableRef();
     const double v[3] = {params[0].value, params[1].value, params[2].value};
     const int len = discrete_table_len(dist, v);
-    if (len <= 0) return nullptr;
+    if (len <= 0) return TableRef();
     double lo, hi;
     (void)sum_bounds(dist, v[0], v[1], v[2], &lo, &hi);
     auto build = [=](double* t, hipStream_t st) {
@@ -370,25 +370,18 @@ double* build_table(int dist, const pbh_param* params, int nparams, hipStream_t 
     };
     const size_t bytes = (size_t)(2 * len + 1) * sizeof(double);
     const double key[4] = {(double)dist, v[0], v[1], v[2]};
-    if (double* t = cached_table(kTabDiscrete, key, 4, bytes, s, build)) return t;
-    double* t = nullptr;
-    if (hipMallocAsync((void**)&t, bytes, s) != hipSuccess) return nullptr;
-    if (!build(t, s)) {
-      (void)hipFreeAsync(t, s);
-      return nullptr;
-    }
-    return t;
+    return acquire_table(kTabDiscrete, key, 4, bytes, s, build);
   }
   if (dist == PBH_DIST_BINOM || dist == PBH_DIST_BERNOULLI || dist == PBH_DIST_NBINOM) {
     const int ns = dist == PBH_DIST_BERNOULLI ? 1 : 2;
-    if (nparams < ns) return nullptr;
+    if (nparams < ns) return TableRef();
     double v[2] = {0.0, 0.0};
     for (int j = 0; j < ns; ++j) {
-      if (params[j].ptr) return nullptr;
+      if (params[j].ptr) return TableRef();
       v[j] = params[j].value;
     }
     const int len = discrete_table_len(dist, v);
-    if (len <= 0) return nullptr;
+    if (len <= 0) return TableRef();
     auto build = [=](double* t, hipStream_t st) {
       const double hdr = (double)len;
       if (hipMemcpyAsync(t, &hdr, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
@@ -403,21 +396,14 @@ double* build_table(int dist, const pbh_param* params, int nparams, hipStream_t 
     };
     const size_t bytes = (size_t)(2 * len + 1) * sizeof(double);
     const double key[3] = {(double)dist, v[0], v[1]};
-    if (double* t = cached_table(kTabDiscrete, key, 3, bytes, s, build)) return t;
-    double* t = nullptr;
-    if (hipMallocAsync((void**)&t, bytes, s) != hipSuccess) return nullptr;
-    if (!build(t, s)) {
-      (void)hipFreeAsync(t, s);
-      return nullptr;
-    }
-    return t;
+    return acquire_table(kTabDiscrete, key, 3, bytes, s, build);
   }
-  if (dist != PBH_DIST_BETA || nparams < 2 || params[0].ptr || params[1].ptr) return nullptr;
+  if (dist != PBH_DIST_BETA || nparams < 2 || params[0].ptr || params[1].ptr) return TableRef();
   return beta_guide_table(params[0].value, params[1].value, s);
 }
 
-double* beta_guide_table(double a, double b, hipStream_t s) {
-  if (!(a > 0.0 && b > 0.0 && isfinite(a) && isfinite(b))) return nullptr;
+TableRef beta_guide_table(double a, double b, hipStream_t s) {
+  if (!(a > 0.0 && b > 0.0 && isfinite(a) && isfinite(b))) return TableRef();
   constexpr int m = sfx::kBetaGuideM;
   auto build = [=](double* t, hipStream_t st) {
     const unsigned g = (unsigned)((m + 63) / 64);
@@ -428,14 +414,7 @@ double* beta_guide_table(double a, double b, hipStream_t s) {
   };
   const size_t bytes = (size_t)4 * m * sizeof(double);
   const double key[2] = {a, b};
-  if (double* t = cached_table(kTabBetaGuide, key, 2, bytes, s, build)) return t;
-  double* t = nullptr;
-  if (hipMallocAsync((void**)&t, bytes, s) != hipSuccess) return nullptr;
-  if (!build(t, s)) {
-    (void)hipFreeAsync(t, s);
-    return nullptr;
-  }
-  return t;
+  return acquire_table(kTabBetaGuide, key, 2, bytes, s, build);
 }
 
 sfx::BetaGuide guide_of(const double* t) {
@@ -1455,7 +1434,7 @@ int launch_ext(int dist, const double* q, int64_t q_stride, const LhsCol* lc, in
     prm.val[j] = params[j].value;
   }
   if (n == 0) return PBH_OK;
-  double* table = build_table(dist, params, nparams, s);
+  TableRef table = build_table(dist, params, nparams, s);
   attach_table(dist, table, prm);
   dim3 g(grid_for(n, 256, 16384)), b(256);
   const LhsCol l = lc ? *lc : LhsCol{0, 1, 0, 0};
@@ -1466,7 +1445,7 @@ int launch_ext(int dist, const double* q, int64_t q_stride, const LhsCol* lc, in
     else
       PBH_TIMED(kKPpf, s, hipLaunchKernelGGL((k_ppf_ext<D, false>), g, b, 0, s, q, q_stride, l, n, prm, out, flag));
   });
-  release_table(table, s);  // stream-ordered: after the kernel (cached tables stay)
+  table.reset();  // stream-ordered: after the kernel (cached tables stay); before the status is read
   if (!known) {
     set_error("ppf: unknown distribution id %d", dist);
     return PBH_ERR_UNSUPPORTED;
@@ -1847,7 +1826,7 @@ int ext_gen_cert_eval(uint64_t seed, int64_t n, uint32_t col, int dist, const do
   return PBH_OK;
 }
 
-double* ext_gen_table(int dist, const double* val, int np, hipStream_t s) {
+TableRef ext_gen_table(int dist, const double* val, int np, hipStream_t s) {
   pbh_param prm[4];
   for (int j = 0; j < 4; ++j) prm[j] = pbh_param{nullptr, j < np ? val[j] : 0.0};
   return build_table(dist, prm, np, s);

@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "pbh_error.h"
+#include "pbh_scope.h"
 #include "pbh_sort.h"
 #include "pbh_timing.h"
 
@@ -841,14 +842,17 @@ int code_sort_buckets(SortBuffers& b, int64_t n, const uint32_t* codes, const do
   // 65536 bucket starts: in `counts` (256 * sort_tiles(n) words) when it is large enough
   uint32_t* start = b.counts;
   const bool own = (int64_t)256 * nt < 65536;
-  if (own) PBH_CHECK_HIP(hipMallocAsync((void**)&start, 65536 * 4, s));
+  Scratch<uint32_t> own_start;  // freed stream-ordered: after the bucket kernels
+  if (own) {
+    PBH_CHECK_HIP(own_start.get(65536 * 4, s));
+    start = own_start;
+  }
   PBH_CHECK_HIP(hipMemsetAsync(start, 0xFF, 65536 * 4, s));
   PBH_TIMED(kKCodeRuns, s,
             hipLaunchKernelGGL(k_bucket_starts, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, keys[cur], n, start);
             hipLaunchKernelGGL(k_code_buckets, dim3(65536 / kCBWaves), dim3(64 * kCBWaves), 0, s, keys[cur], b.vals[cur], x, n, start,
                                eqprev, flags));
   PBH_CHECK_LAUNCH();
-  if (own) PBH_CHECK_HIP(hipFreeAsync(start, s));
   *out_buf = cur;
   return PBH_OK;
 }

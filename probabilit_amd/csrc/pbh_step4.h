@@ -4,6 +4,7 @@
 #pragma once
 
 #include "pbh_common.h"
+#include "pbh_scope.h"
 
 namespace pbh {
 
@@ -91,9 +92,9 @@ inline bool gen_discrete(int dist) {
          dist == PBH_DIST_BETABINOM || dist == PBH_DIST_HYPERGEOM || dist == PBH_DIST_NHYPERGEOM ||
          dist == PBH_DIST_YULESIMON || dist == PBH_DIST_ZIPFIAN;
 }
-int gen_create(uint64_t seed, int64_t n, int col, int dist, const pbh_param* params, int nparams, GenColumn** out,
+// (the handle frees the column and gives its tables back on s, or on the stream its owner sets)
+int gen_create(uint64_t seed, int64_t n, int col, int dist, const pbh_param* params, int nparams, GenHandle* out,
                hipStream_t s);
-void gen_destroy(GenColumn* g, hipStream_t s);
 // out[t - t0] = the column's value in stratum t (see lhs_sorted_ppf); out may be NULL when
 // counts (ties, inversions) is given.  heads: the run heads, unordered, at most hcap of them --
 // every t in (t0, t0 + nt) whose value differs from stratum t - 1's, and t0 itself when t0 = 0;

@@ -6,6 +6,7 @@
 #include <functional>
 
 #include "pbh_common.h"
+#include "pbh_scope.h"
 
 namespace pbh {
 
@@ -16,14 +17,12 @@ enum TableKind : int {
   kTabDiscrete = 4,    // binom / bernoulli / nbinom CDF + complement (key: dist id, parameters)
 };
 
-// The table of (kind, key[0 .. nkey)): built once per process and device by `build` on stream s
-// into a persistent allocation of `bytes`, then reused by every later call (s waits for the
-// build's completion event).  nullptr when the cache is full or the build fails: the caller then
-// builds a table of its own for this call.
-double* cached_table(int kind, const double* key, int nkey, size_t bytes, hipStream_t s,
-                     const std::function<bool(double*, hipStream_t)>& build);
+using TableBuild = std::function<bool(double*, hipStream_t)>;
 
-// The end of a call's use of a table: hipFreeAsync on s unless it belongs to the cache.
-void release_table(double* t, hipStream_t s);
+// The table of (kind, key[0 .. nkey)), held until the ref leaves: built once per process and
+// device by `build` on stream s into a persistent allocation of `bytes`, then reused by every
+// later call (s waits for the build's completion event); when the cache is full, a table of this
+// call's own in a stream-ordered allocation.  Empty when the build or the allocation fails.
+TableRef acquire_table(int kind, const double* key, int nkey, size_t bytes, hipStream_t s, const TableBuild& build);
 
 }  // namespace pbh

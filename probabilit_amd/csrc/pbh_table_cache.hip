@@ -58,8 +58,10 @@ static TableCache& cache() {
   return c;
 }
 
-double* cached_table(int kind, const double* key, int nkey, size_t bytes, hipStream_t s,
-                     const std::function<bool(double*, hipStream_t)>& build) {
+// The cache's table of (kind, key), built into a persistent allocation on first use; nullptr
+// when the cache declines (an oversized table, every entry in use) or the build fails.
+static double* cached_table(int kind, const double* key, int nkey, size_t bytes, hipStream_t s,
+                            const TableBuild& build) {
   if (nkey < 0 || nkey > 4) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -106,7 +108,8 @@ double* cached_table(int kind, const double* key, int nkey, size_t bytes, hipStr
   return e.ptr;
 }
 
-void release_table(double* t, hipStream_t s) {
+// The end of a call's use of a table: hipFreeAsync on s unless it belongs to the cache.
+static void release_table(double* t, hipStream_t s) {
   if (!t) return;
   {
     TableCache& c = cache();
@@ -120,6 +123,17 @@ void release_table(double* t, hipStream_t s) {
       }
   }
   (void)hipFreeAsync(t, s);
+}
+
+void TableRelease::operator()(double* t, hipStream_t s) const { release_table(t, s); }
+
+TableRef acquire_table(int kind, const double* key, int nkey, size_t bytes, hipStream_t s, const TableBuild& build) {
+  if (double* t = cached_table(kind, key, nkey, bytes, s, build)) return TableRef(t, s);
+  double* t = nullptr;
+  if (hipMallocAsync((void**)&t, bytes, s) != hipSuccess) return TableRef();
+  TableRef own(t, s);  // freed (stream-ordered) if the build fails
+  if (!build(t, s)) own.reset();
+  return own;
 }
 
 }  // namespace pbh
